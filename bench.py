@@ -16,6 +16,11 @@ BASELINE.json's metric has two halves; the ONE JSON line rank 0 prints carries b
              overlapped segments dealt to the ranks (--segment-concurrency = 2 chains at a time per GPU), stitched on rank 0
              with every seam verified (strong scaling).
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: it sets up the decoders and the
+stream, runs W untimed steps and K timed ones, writes the last timed step's decoded bits when --dump-outputs DIR is
+given, and prints the line (top-level fields and `config`).  Everything else -- host_buffers, the single-decoder pass
+and `roofline`, the BER check, `frames`, `chain`, `stress`, `cpu_baseline` -- runs only with --full.
+
 N > 1: `python bench.py --gpus N` starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child process
 (before anything here touches a device); one rank per GPU, RCCL only for the barrier / MAX / SUM / the gather of decoded
 bits: every rank works on its own independent stream and capture -- segments shard one per GPU, no collective in the
@@ -46,6 +51,7 @@ HBM_PEAK_GBS = 8000.0
 CLOCK_GHZ = 2.4                                                 # MI355X max shader clock (MI355X_MICROARCH.md)
 N_SIMD = 256 * 4
 WAVES_PER_LAUNCH = 256 * 16                                     # k_acs_lds15: 256 workgroups x 1024 threads
+DUMP_LIMIT_BYTES = 64_000_000                                   # --dump-outputs: all arrays together, float32
 
 
 def load_pkg():
@@ -217,6 +223,18 @@ def pmc_constants(kern):
             if tj.get("kernel") == kern:
                 return tj, "profiles/" + tname
     return {}, None
+
+
+def dump_outputs(outdir, named, limit_bytes=DUMP_LIMIT_BYTES):
+    """--dump-outputs: each (name, array) as outdir/<name>.npy in float32.  `limit_bytes` is shared out equally; an array
+    longer than its share is written as a sample at fixed positions (seeded, sorted), the same in every run."""
+    os.makedirs(outdir, exist_ok=True)
+    for name, arr, share in named:
+        x = np.asarray(arr).ravel()
+        n = min(len(x), (int(limit_bytes * share) - 4096) // 4)          # 4 KiB of the share left for the .npy header
+        if n < len(x):
+            x = x[np.sort(np.random.default_rng(0).choice(len(x), n, replace=False))]
+        np.save(os.path.join(outdir, name + ".npy"), x.astype(np.float32))
 
 
 def chain_check(bits, sent):
@@ -438,6 +456,65 @@ def stress_record(a, ctx, capture):
     return rec
 
 
+def kernel_roofline(a, launches, ms, steps_timed, single):
+    """`roofline` of the headline (--full): k_acs_lds15's launch times from the HIP events of the single-decoder pass
+    (lone launch) and of the timed steps (launch pair), against the VALU-issue and HBM roofs (committed PMC constants)."""
+    avg_ms = ms / launches if launches else float("nan")
+    steps_per_launch = steps_timed / launches if launches else 0
+    kern = "k_acs_lds15"
+    pmc, psrc = pmc_constants(kern)
+    traffic = pmc.get("hbm_bytes_per_launch")
+    valu = pmc.get("valu_insts_per_wave")
+    cyc = pmc.get("valu_cycles_per_inst", 4.2)
+    alg = ALG_BYTES_PER_STEP * steps_per_launch
+    peak = N_SIMD * CLOCK_GHZ / cyc
+
+    def fractions(t):
+        """the kernel's roofs at t seconds per launch: VALU issue (the binding one), physical HBM, SURVEY 8(d)'s algorithmic bytes"""
+        f = {"avg_launch_ms": round(t * 1e3, 6), "algorithmic_GBps": round(alg / t / 1e9, 1),
+             "algorithmic_x_peak": round(alg / t / 1e9 / HBM_PEAK_GBS, 4)}
+        if traffic:
+            f["hbm"] = {"bound": "hbm", "achieved": round(traffic / t / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(traffic / t / 1e9 / HBM_PEAK_GBS, 4), "traffic": traffic}
+            f["hbm_physical_GBps"], f["hbm_physical_frac"] = f["hbm"]["achieved"], f["hbm"]["frac"]
+        if valu:
+            ach = valu * WAVES_PER_LAUNCH / t / 1e9
+            f.update({"achieved": round(ach, 1), "peak": round(peak, 1), "unit": "G wave-instructions/s (VALU)",
+                      "frac": round(ach / peak, 4)})
+        elif traffic:
+            f.update({"achieved": f["hbm"]["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": f["hbm"]["frac"]})
+        return f
+
+    roof = {"kernel": kern, "bound": "valu-issue" if valu else "hbm", "trellis_steps_per_launch": steps_per_launch,
+            "traffic": traffic, "traffic_unit": "HBM bytes per launch (PMC FETCH_SIZE x2 + WRITE_SIZE, %s)" % psrc,
+            "algorithmic_bytes_per_step": ALG_BYTES_PER_STEP, "algorithmic_bytes_per_launch": int(alg),
+            "valu_insts_per_wave": valu, "valu_cycles_per_inst": cyc,
+            "note": "15 trellis steps share one pass over the path metrics, so a launch is bound by VALU issue, not by HBM: "
+                    "frac = VALU instructions per wave x 4 waves per SIMD x %.1f cycles per instruction (measured for this VOP3P / "
+                    "VOP2 mix, profiles/r01_valu_rate.txt) / (time per launch x %.1f GHz); `hbm` = the same launch against the "
+                    "8 TB/s HBM peak with the bytes it physically moves; the SURVEY 8(d) algorithmic bytes exceed what is "
+                    "moved (algorithmic_x_peak: fusion depth, not efficiency)" % (cyc, CLOCK_GHZ)}
+    lone = fractions(avg_ms * 1e-3) if launches else None
+    if lone:
+        lone.update({"launches_timed": launches,
+                     "measured_on": ("the single-decoder reference pass of this run" if a.split > 1 else "the timed steps") +
+                                    ": one %s at a time on the GPU; HIP events on the decoder's own stream around runs of "
+                                    "back-to-back launches" % kern})
+    if single and single.get("split_avg_launch_ms"):
+        # the timed region: two decoders' launches side by side; decoder 0's launch period covers one launch of EACH
+        # decoder, i.e. two launches complete per period
+        tp = single["split_avg_launch_ms"] * 1e-3
+        roof.update(fractions(tp / 2))
+        roof.update({"launch_pair_ms": single["split_avg_launch_ms"],
+                     "measured_on": "the timed steps: this stream's two decoders run their launch chains side by side (HIP events on "
+                                    "decoder 0's stream; one launch of each decoder per period, avg_launch_ms = period / 2); the lone "
+                                    "launch is under single_decoder",
+                     "single_decoder": lone})
+    elif lone:
+        roof.update(lone)
+    return roof
+
+
 def spawn_ranks(n):
     """One process per GPU: `python -m torch.distributed.run --nnodes=1 --nproc-per-node n bench.py <same arguments>` as a
     child of this (GPU-free) process; returns its exit code.  Rendezvous on 127.0.0.1 and a free port."""
@@ -504,13 +581,19 @@ def main():
     ap.add_argument("--split", type=int, default=2,
                     help="> 1: decode each stream with this many decoders working on consecutive parts at the same time, "
                          "verified at the seams (v224hip_stream_decode_split): same output as one decoder.  1: one "
-                         "decoder per stream.  With > 1 a single-decoder pass is timed too (1 step) and reported "
-                         "beside the headline, together with the check that both outputs are identical")
+                         "decoder per stream.  With > 1 and --full a single-decoder pass is timed too (1 step) and "
+                         "reported beside the headline, together with the check that both outputs are identical")
     ap.add_argument("--split-warm", type=int, default=14280, help="warm-up bits before each part (14 chunks)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: host_buffers, the single-decoder pass, roofline, the BER check, frames, "
+                         "chain, stress and the CPU baselines (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the decoded bits of the last timed step as DIR/decoded_bits_seg<g>.npy "
+                         "(float32; a fixed sample of each stream when all together exceed 64 MB)")
     ap.add_argument("--cpu-bits", type=int, default=6000)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-frames", action="store_true", help="skip the framed-batch record")
-    ap.add_argument("--no-chain", action="store_true", help="skip the chain half of the metric (kernel profiling runs)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full or --workload chain: skip the CPU baselines")
+    ap.add_argument("--no-frames", action="store_true", help="with --full: skip the framed-batch record")
+    ap.add_argument("--no-chain", action="store_true", help="with --full: skip the chain half of the metric (kernel profiling runs)")
     ap.add_argument("--workload", choices=["viterbi", "chain"], default="viterbi")
     ap.add_argument("--chain-seconds", type=float, default=60.0)
     ap.add_argument("--chain-rate", type=float, default=250000.0)
@@ -520,7 +603,7 @@ def main():
     ap.add_argument("--chain-segments", type=int, default=1,
                     help="> 1: cut ONE capture into this many overlapped segments over all ranks (configs[4])")
     ap.add_argument("--chain-warm-blocks", type=int, default=7)
-    ap.add_argument("--no-stress", action="store_true", help="skip the configs[4] record (10 MS/s, 64 overlapped segments)")
+    ap.add_argument("--no-stress", action="store_true", help="with --full: skip the configs[4] record (10 MS/s, 64 overlapped segments)")
     ap.add_argument("--stress-blocks", type=int, default=128,
                     help="blocks of 2^23 samples in the stress capture (64 B: every one of the 64 segments owns B blocks and carries 7 "
                          "warm-up blocks; B = 2: 107 s of signal, 4.3 GB)")
@@ -531,6 +614,10 @@ def main():
                     help="no device work: every rank runs a stand-in step through the same launcher / sharding / fence / MAX "
                          "code on gloo and rank 0 prints the line (CPU test of the N-rank path)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and (a.workload != "viterbi" or a.dry_ranks):
+        ap.error("--dump-outputs writes the outputs of the default (viterbi) workload")
 
     # `python bench.py --gpus N`, N > 1, outside torchrun: start the N ranks ourselves -- as a CHILD process, before this
     # process has imported torch.cuda or loaded a HIP library (never an exec of a process that touched the GPU)
@@ -545,7 +632,7 @@ def main():
     if a.dry_ranks:
         return dry_ranks(a, rank, world)
     # the stress record's capture: made now, by forked workers, while this process has not touched a device yet
-    capture = stress_capture(a, world) if a.workload == "viterbi" and not a.no_chain and not a.no_stress else None
+    capture = stress_capture(a, world) if a.full and a.workload == "viterbi" and not a.no_chain and not a.no_stress else None
 
     import torch
     import torch.distributed as dist
@@ -616,8 +703,8 @@ def main():
 
     dd = dist if world > 1 else None
     fence = harness.make_fence(dd, torch.cuda.synchronize)
-    single = None
-    if a.split > 1:
+    single = launches = ms = steps_timed = None
+    if a.full and a.split > 1:
         # reference pass: ONE decoder per stream (1 warm-up + 1 timed step); its kernel timing feeds `roofline`, its
         # output is what the split decode has to reproduce byte for byte
         harness.timed_steps(step_single, 0, 1, fence)
@@ -628,144 +715,90 @@ def main():
         dec.set_option("profile", 0)
         dt1 = harness.max_over_ranks(dd, torch, dt1, redev)
         single_out = segs[0]["d_out"].to_numpy(np.uint8).copy()
-        harness.timed_steps(step_split, 0, a.warmup, fence)
-        redone[0] = 0
+    step = step_split if a.split > 1 else step_single
+    harness.timed_steps(step, 0, a.warmup, fence)
+    redone[0] = 0
+    if a.full:                                           # HIP events on decoder 0's stream: the kernel timing of `roofline`
         dec.set_option("profile", 4)
         dec.acs_stats(reset=True)
-        dt_local = harness.timed_steps(step_split, a.steps, 0, fence)
-        l2, ms2, st2 = dec.acs_stats()
+    dt_local = harness.timed_steps(step, a.steps, 0, fence)
+    if a.full:
+        stats = dec.acs_stats()
         dec.set_option("profile", 0)
-        single = {"value": round(2 * nbits * nseg / dt1 / 1e6, 4), "ms_per_step": round(dt1 * 1e3, 3),
-                  "identical_output": bool(np.array_equal(single_out, segs[0]["d_out"].to_numpy(np.uint8))),
-                  "split_avg_launch_ms": round(ms2 / l2, 6) if l2 else None}
-    else:
-        harness.timed_steps(step_single, 0, a.warmup, fence)
-        dec.set_option("profile", 4)
-        dec.acs_stats(reset=True)
-        dt_local = harness.timed_steps(step_single, a.steps, 0, fence)
-        launches, ms, steps_timed = dec.acs_stats()
-        dec.set_option("profile", 0)
+        if a.split > 1:
+            l2, ms2, _ = stats
+            single = {"value": round(2 * nbits * nseg / dt1 / 1e6, 4), "ms_per_step": round(dt1 * 1e3, 3),
+                      "identical_output": bool(np.array_equal(single_out, segs[0]["d_out"].to_numpy(np.uint8))),
+                      "split_avg_launch_ms": round(ms2 / l2, 6) if l2 else None}
+        else:
+            launches, ms, steps_timed = stats
     dt = harness.max_over_ranks(dd, torch, dt_local, redev)
     per_rank = harness.gather_per_rank(dd, round(dt_local / a.steps * 1e3, 3))
+    if a.dump_outputs:                                   # what a caller of the timed path receives: the last step's bits
+        dump_outputs(a.dump_outputs, [("decoded_bits_seg%d" % g, sg["d_out"].to_numpy(np.uint8), 1.0 / nseg)
+                                      for g, sg in zip(mine, segs)])
 
-    # SURVEY 8(d) config 2's region -- "first kernel enqueue -> last output bit in host memory, H2D of the input
-    # included": ONE more step that starts from host symbols and ends with the bits in a host array.  Reported beside
-    # `value` (which, by the bench contract, is the rate with the inputs resident in HBM).
-    resident_out = segs[0]["d_out"].to_numpy(np.uint8).copy()
-    host_out = [np.empty(nbits, np.uint8) for _ in segs]
-    L = pkg.v224_lib()
+    host_buffers = check = frames = chain = stress = None
+    if a.full:
+        # SURVEY 8(d) config 2's region -- "first kernel enqueue -> last output bit in host memory, H2D of the input
+        # included": ONE more step that starts from host symbols and ends with the bits in a host array.  Reported beside
+        # `value` (which, by the bench contract, is the rate with the inputs resident in HBM).
+        resident_out = segs[0]["d_out"].to_numpy(np.uint8).copy()
+        host_out = [np.empty(nbits, np.uint8) for _ in segs]
+        L = pkg.v224_lib()
 
-    def step_host_buffers():
-        for sg, ho in zip(segs, host_out):
-            if L.v224hip_h2d(sg["d_syms"].ptr, sg["syms"].ctypes.data, sg["syms"].nbytes) != 0:
-                raise RuntimeError("h2d failed")
-        (step_split if a.split > 1 else step_single)()
-        for sg, ho in zip(segs, host_out):
-            if L.v224hip_d2h(ho.ctypes.data, sg["d_out"].ptr, ho.nbytes) != 0:
-                raise RuntimeError("d2h failed")
+        def step_host_buffers():
+            for sg, ho in zip(segs, host_out):
+                if L.v224hip_h2d(sg["d_syms"].ptr, sg["syms"].ctypes.data, sg["syms"].nbytes) != 0:
+                    raise RuntimeError("h2d failed")
+            step()
+            for sg, ho in zip(segs, host_out):
+                if L.v224hip_d2h(ho.ctypes.data, sg["d_out"].ptr, ho.nbytes) != 0:
+                    raise RuntimeError("d2h failed")
 
-    dt_host = harness.max_over_ranks(dd, torch, harness.timed_steps(step_host_buffers, 1, 0, fence), redev)
-    host_same = bool(np.array_equal(host_out[0], resident_out))
-    d_out, bits, noise_mask = segs[0]["d_out"], segs[0]["bits"], segs[0]["noise_mask"]
+        dt_host = harness.max_over_ranks(dd, torch, harness.timed_steps(step_host_buffers, 1, 0, fence), redev)
+        host_buffers = {"value": round(2 * nbits * nseg / dt_host / 1e6, 4), "ms_per_step": round(dt_host * 1e3, 3),
+                        "steps": 1, "identical_output": bool(np.array_equal(host_out[0], resident_out)),
+                        "what": "SURVEY 8(d) config 2's region: %.1f MB of symbols H2D (pageable numpy array, "
+                                "blocking copy), the whole decode, %.1f MB of bits D2H into a host array -- "
+                                "PCIe inclusive, never the headline" % (2 * nbits / 1e6, nbits / 1e6)}
+        d_out, bits, noise_mask = segs[0]["d_out"], segs[0]["bits"], segs[0]["noise_mask"]
 
-    # sanity: decoded bits equal sent bits away from the noise blocks (does not replace tests/)
-    out = d_out.to_numpy(np.uint8)
-    dec_bits = out[a.delay + 23:]
-    ref_bits = bits[1:1 + len(dec_bits)]
-    clean = np.ones(len(dec_bits), bool)
-    nz = np.flatnonzero(noise_mask[::2])
-    for i in nz[:: 256]:
-        lo = max(0, i - 1200); clean[lo:i + 1200] = False
-    ber = float(np.mean(dec_bits[clean] != ref_bits[clean])) if clean.any() else -1.0
+        # sanity: decoded bits equal sent bits away from the noise blocks (does not replace tests/)
+        out = d_out.to_numpy(np.uint8)
+        dec_bits = out[a.delay + 23:]
+        ref_bits = bits[1:1 + len(dec_bits)]
+        clean = np.ones(len(dec_bits), bool)
+        nz = np.flatnonzero(noise_mask[::2])
+        for i in nz[:: 256]:
+            lo = max(0, i - 1200); clean[lo:i + 1200] = False
+        ber = float(np.mean(dec_bits[clean] != ref_bits[clean])) if clean.any() else -1.0
+        check = {"ber_clean": ber, "bits": int(clean.sum())}
     for sg in segs:                                     # free the decoders (2.2 GiB rings) before the chain runs
         for d in sg["decs"]:
             d.close()
         sg["d_syms"].free(); sg["d_out"].free()
 
-    frames = frames_record(pkg, synth) if not a.no_frames else None
-    chain = None
-    if not a.no_chain:
-        chain = chain_record(a, ctx, a.chain_seconds, a.chain_rate, a.chain_bin, a.chain_steps or a.steps, max(1, a.warmup),
-                             world == 1 and not a.no_cpu)
-        pkg.release_chain_objects()
-    stress = None
-    if capture is not None:
-        stress = stress_record(a, ctx, capture)
-        capture = None
-        pkg.release_chain_objects()
+    if a.full:
+        frames = frames_record(pkg, synth) if not a.no_frames else None
+        if not a.no_chain:
+            chain = chain_record(a, ctx, a.chain_seconds, a.chain_rate, a.chain_bin, a.chain_steps or a.steps, max(1, a.warmup),
+                                 world == 1 and not a.no_cpu)
+            pkg.release_chain_objects()
+        if capture is not None:
+            stress = stress_record(a, ctx, capture)
+            capture = None
+            pkg.release_chain_objects()
 
     if rank == 0:
         total_syms = 2 * nbits * nseg * a.steps
-        avg_ms = ms / launches if launches else float("nan")
-        steps_per_launch = steps_timed / launches if launches else 0
-        kern = "k_acs_lds15"
-        pmc, psrc = pmc_constants(kern)
-        traffic = pmc.get("hbm_bytes_per_launch")
-        valu = pmc.get("valu_insts_per_wave")
-        cyc = pmc.get("valu_cycles_per_inst", 4.2)
-        alg = ALG_BYTES_PER_STEP * steps_per_launch
-        peak = N_SIMD * CLOCK_GHZ / cyc
-
-        def fractions(t):
-            """the kernel's roofs at t seconds per launch: VALU issue (the binding one), physical HBM, SURVEY 8(d)'s algorithmic bytes"""
-            f = {"avg_launch_ms": round(t * 1e3, 6), "algorithmic_GBps": round(alg / t / 1e9, 1),
-                 "algorithmic_x_peak": round(alg / t / 1e9 / HBM_PEAK_GBS, 4)}
-            if traffic:
-                f["hbm"] = {"bound": "hbm", "achieved": round(traffic / t / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                            "frac": round(traffic / t / 1e9 / HBM_PEAK_GBS, 4), "traffic": traffic}
-                f["hbm_physical_GBps"], f["hbm_physical_frac"] = f["hbm"]["achieved"], f["hbm"]["frac"]
-            if valu:
-                ach = valu * WAVES_PER_LAUNCH / t / 1e9
-                f.update({"achieved": round(ach, 1), "peak": round(peak, 1), "unit": "G wave-instructions/s (VALU)",
-                          "frac": round(ach / peak, 4)})
-            elif traffic:
-                f.update({"achieved": f["hbm"]["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": f["hbm"]["frac"]})
-            return f
-
-        roof = {"kernel": kern, "bound": "valu-issue" if valu else "hbm", "trellis_steps_per_launch": steps_per_launch,
-                "traffic": traffic, "traffic_unit": "HBM bytes per launch (PMC FETCH_SIZE x2 + WRITE_SIZE, %s)" % psrc,
-                "algorithmic_bytes_per_step": ALG_BYTES_PER_STEP, "algorithmic_bytes_per_launch": int(alg),
-                "valu_insts_per_wave": valu, "valu_cycles_per_inst": cyc,
-                "note": "15 trellis steps share one pass over the path metrics, so a launch is bound by VALU issue, not by HBM: "
-                        "frac = VALU instructions per wave x 4 waves per SIMD x %.1f cycles per instruction (measured for this VOP3P / "
-                        "VOP2 mix, profiles/r01_valu_rate.txt) / (time per launch x %.1f GHz); `hbm` = the same launch against the "
-                        "8 TB/s HBM peak with the bytes it physically moves; the SURVEY 8(d) algorithmic bytes exceed what is "
-                        "moved (algorithmic_x_peak: fusion depth, not efficiency)" % (cyc, CLOCK_GHZ)}
-        lone = fractions(avg_ms * 1e-3) if launches else None
-        if lone:
-            lone.update({"launches_timed": launches,
-                         "measured_on": ("the single-decoder reference pass of this run" if a.split > 1 else "the timed steps") +
-                                        ": one %s at a time on the GPU; HIP events on the decoder's own stream around runs of "
-                                        "back-to-back launches" % kern})
-        if single and single.get("split_avg_launch_ms"):
-            # the timed region: two decoders' launches side by side; decoder 0's launch period covers one launch of EACH
-            # decoder, i.e. two launches complete per period
-            tp = single["split_avg_launch_ms"] * 1e-3
-            roof.update(fractions(tp / 2))
-            roof.update({"launch_pair_ms": single["split_avg_launch_ms"],
-                         "measured_on": "the timed steps: this stream's two decoders run their launch chains side by side (HIP events on "
-                                        "decoder 0's stream; one launch of each decoder per period, avg_launch_ms = period / 2); the lone "
-                                        "launch is under single_decoder",
-                         "single_decoder": lone})
-        elif lone:
-            roof.update(lone)
-        res = {
-            "metric": "Viterbi K=24 Msymbols/s",
-            "value": round(total_syms / dt / 1e6, 4), "unit": "Msymbols/s",
-            "n_gpus": world, "ranks_seen": ctx["ranks_seen"], "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": round(dt / a.steps * 1e3, 3), "ms_per_step_per_rank": per_rank,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "u16", "data": "synthetic",
-            "config": {"workload": "viterbi224 ACS+chainback streaming, 2^23 states, 8-bit soft syms, "
-                                   "decode delay %d, %d symbols per GPU per step" % (a.delay, 2 * nbits),
-                       "residency": "value: symbols resident in HBM when the timed region starts, decoded bits left in HBM "
-                                    "(bench contract); host_buffers: the same step from host symbols to host bits",
-                       "host_buffers": {"value": round(2 * nbits * nseg / dt_host / 1e6, 4), "ms_per_step": round(dt_host * 1e3, 3),
-                                        "steps": 1, "identical_output": host_same,
-                                        "what": "SURVEY 8(d) config 2's region: %.1f MB of symbols H2D (pageable numpy array, "
-                                                "blocking copy), the whole decode, %.1f MB of bits D2H into a host array -- "
-                                                "PCIe inclusive, never the headline" % (2 * nbits / 1e6, nbits / 1e6)},
-                       "engine": "lds15", "steps_per_launch": 15,
+        config = {"workload": "viterbi224 ACS+chainback streaming, 2^23 states, 8-bit soft syms, "
+                              "decode delay %d, %d symbols per GPU per step" % (a.delay, 2 * nbits),
+                  "residency": "value: symbols resident in HBM when the timed region starts, decoded bits left in HBM "
+                               "(bench contract)" + ("; host_buffers: the same step from host symbols to host bits" if a.full else "")}
+        if host_buffers is not None:
+            config["host_buffers"] = host_buffers
+        config.update({"engine": "lds15", "steps_per_launch": 15,
                        "chunk_bits": chunk,
                        "segments_per_gpu": a.segments_per_gpu, "parallelism": "segments x%d" % nseg,
                        "decoders_per_stream": a.split,
@@ -774,23 +807,34 @@ def main():
                                    "part j > 0 warms up %d bits early and its path metrics are compared with the previous "
                                    "decoder's at the seam (all 2^23 states equal => identical continuation, else the part is "
                                    "decoded again): v224hip_stream_decode_split" % (a.split, a.split, a.split_warm),
-                           "parts_redone": redone[0], "single_decoder": single}},
-            "roofline": roof,
-            "check": {"ber_clean": ber, "bits": int(clean.sum())},
+                           "parts_redone": redone[0]},
+                       "full": a.full})
+        if single is not None:
+            config["split"]["single_decoder"] = single
+        res = {
+            "metric": "Viterbi K=24 Msymbols/s",
+            "value": round(total_syms / dt / 1e6, 4), "unit": "Msymbols/s",
+            "n_gpus": world, "ranks_seen": ctx["ranks_seen"], "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": round(dt / a.steps * 1e3, 3), "ms_per_step_per_rank": per_rank,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "u16", "data": "synthetic",
+            "config": config,
         }
-        if world == 1 and not a.no_cpu:
-            res["cpu_baseline"] = cpu_baseline(a.cpu_bits)
-            res["speedup_vs_cpu_1core"] = round(res["value"] / res["cpu_baseline"]["value"], 1)
-        if frames is not None:
-            res["frames"] = frames
-        if chain is not None:
-            res["chain"] = chain
-        if stress is not None:
-            res["stress"] = stress
+        if a.full:
+            res["roofline"] = kernel_roofline(a, launches, ms, steps_timed, single)
+            res["check"] = check
+            if world == 1 and not a.no_cpu:
+                res["cpu_baseline"] = cpu_baseline(a.cpu_bits)
+                res["speedup_vs_cpu_1core"] = round(res["value"] / res["cpu_baseline"]["value"], 1)
+            if frames is not None:
+                res["frames"] = frames
+            if chain is not None:
+                res["chain"] = chain
+            if stress is not None:
+                res["stress"] = stress
         print(json.dumps(res), flush=True)
     if world > 1:
         dist.destroy_process_group()
-
 
 if __name__ == "__main__":
     main()

@@ -2,6 +2,8 @@
 import ctypes as C
 import os
 import re
+import subprocess
+import sys
 
 import pytest
 
@@ -35,8 +37,12 @@ def test_reference_api_signature_names():
 
 
 def test_no_cpu_fallback_without_gpu():
-    import torch
-    if torch.cuda.is_available():
+    # asked in a child process: torch brings its own HIP runtime, and started in this process after the package's
+    # libraries are loaded it would sit beside theirs and leave every later in-process GPU test without a device
+    probe = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.is_available())"],
+                           capture_output=True, text=True, timeout=300)
+    assert probe.returncode == 0, probe.stderr[-2000:]
+    if probe.stdout.split()[-1:] == ["True"]:
         pytest.skip("GPU present")
     pkg = load_pkg()
     with pytest.raises(RuntimeError):

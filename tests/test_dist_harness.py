@@ -189,3 +189,24 @@ def test_bench_pmc_constants_match_the_committed_kernel_record():
     import subprocess, sys
     h = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120).stdout
     assert "--segment-concurrency" in h
+    assert "--full" in h and "--dump-outputs" in h
+
+
+def test_bench_dump_outputs_float32_capped_and_fixed(tmp_path):
+    """bench.py --dump-outputs: one float32 .npy per array, all of them together within the byte limit; an array longer
+    than its share is written as a sample at fixed, sorted positions, the same from run to run."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    small = (np.arange(3000) % 2).astype(np.uint8)
+    big = np.arange(100000, dtype=np.float64)                        # values = positions: shows which were kept
+    limit = 2 * (4096 + 4 * 20000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), [("small", small, 0.5), ("big", big, 0.5)], limit_bytes=limit)
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in ("small", "big")}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert np.array_equal(got["small"], small.astype(np.float32))
+    assert len(got["big"]) == 20000 and np.all(np.diff(got["big"]) > 0) and got["big"][-1] < len(big)
+    assert sum(os.path.getsize(str(tmp_path / "a" / (n + ".npy"))) for n in got) <= limit
+    assert np.array_equal(np.load(str(tmp_path / "b" / "big.npy")), got["big"])
