@@ -42,7 +42,7 @@ int v224hip_update_dev(void *p, const uint8_t *d_syms, int nbits);
 
 /* Streaming block decode == for each of nbits: update(1 bit); out[i] = decodebit(delay, 0).
  * out[i] is 0/1, or 0xff while fewer than `delay` steps have run since init (vdecode.c:151-158
- * suppresses exactly those).  Needs len >= delay + v224hip_stream_chunk(p) (twice the chunk with V224HIP_TB_STREAM=1).
+ * suppresses exactly those).  Needs len >= delay + v224hip_stream_chunk(p).
  * `syms`/`out` are host buffers in the first form, device buffers in the _dev form. */
 int v224hip_stream_decode(void *p, const uint8_t *syms, int nbits, int delay, uint8_t *out);
 int v224hip_stream_decode_dev(void *p, const uint8_t *d_syms, int nbits, int delay, uint8_t *d_out);
@@ -55,7 +55,7 @@ int v224hip_stream_chunk(void *p);                 /* bits per internal chunk (o
  * every later decision of the two is equal (the recursion port.c:168-181 only ever compares metrics), so decoder j's
  * output from its part on is what decoder j-1 would have gone on to produce.  If they are not, the rest of the stream
  * is decoded again by decoder j-1 from where it stands; *nfallback = number of parts redone (0 in practice with a
- * warm-up of a few thousand bits).  Device buffers; all decoders on one device, same chunk, len >= delay + 2*chunk.
+ * warm-up of a few thousand bits).  Device buffers; all decoders on one device, same chunk, len >= delay + chunk.
  * out[] is exactly what init(0) + v224hip_stream_decode_dev() of one decoder writes. */
 int v224hip_stream_decode_split(void *const *decoders, int ndec, const uint8_t *d_syms, int nbits, int delay,
                                 uint8_t *d_out, int warm_bits, int *nfallback);

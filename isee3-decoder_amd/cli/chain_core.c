@@ -223,11 +223,9 @@ static int vd_init(void *h, int s) {
  * verified at the seam): same bits, two launch chains on the GPU instead of one.  But two 1024-thread workgroups per CU
  * are ALL the wave slots a CU has: while pmdemod / symdemod still have kernels to run, a second decoder starves them
  * (measured: front-end 13 -> 50 ms, chain 40 -> 54 ms).  So a block is shared only once the front end has finished --
- * typically the last, longest block.  ISEE3_CHAIN_SHARE=0 never shares, =2 shares whenever a block is long enough. */
+ * typically the last, longest block. */
 static int vd_stream_any(vd_ctx *c, const unsigned char *s, int n, int d, unsigned char *o) {
-  const char *e = getenv("ISEE3_CHAIN_SHARE");
-  const int mode = e ? atoi(e) : 1;
-  const int may = mode == 2 || (mode == 1 && c->front_done && *c->front_done);
+  const int may = c->front_done && *c->front_done;
   if (may && 5 * n >= 11 * VD_SHARE_WARM && !c->d[1]) {
     c->d[1] = create_viterbi224(c->len);
     if (c->d[1]) v224hip_set_option(c->d[1], "chunk", g_chunk);
@@ -240,8 +238,6 @@ static int vd_stream(void *h, const unsigned char *s, int n, int d, unsigned cha
  * is then noticed within a few ms, and everything that is left goes to two decoders as ONE long block */
 static unsigned long vd_read_limit(void *h) {
   vd_ctx *c = h;
-  const char *e = getenv("ISEE3_CHAIN_SHARE");
-  if (e && atoi(e) == 2) return 0ul;
   return (c->front_done && !*c->front_done) ? 8192ul : 0ul;
 }
 static int vd_whole(void *h, const unsigned char *s, long long n, int d, unsigned char *o) {
@@ -429,14 +425,13 @@ static void *pm_thread(void *p) {
   pm_arg *a = p;
   pmdemod_engine e = { pm_create, pm_dechirp, pm_load, pm_peak, pm_mix, pm_destroy, pm_load_dev, pm_mix_dev, NULL, NULL, NULL, NULL };
   /* Two pmdemod handles in turn, block k+1's transform enqueued before block k's peak is awaited (pmdemod_core.h): on for a
-   * capture that lies in device memory, off for one in host memory (there the next block's staged H2D copy queues in front
-   * of this block's spin-down: 7 % slower); ISEE3_CHAIN_PM_PIPELINE=0 / 1 overrides.  Measured with six launches per block
-   * (profiles/r03ar_*): pmdemod's engine time 17.8 -> 14-15 ms at 10 MS/s, chain 14.51-14.65 -> 14.72-14.82 Gsamples/s;
-   * 5.6 -> 2.3 ms at 250 kS/s, chain the same (its front end is paced by symdemod's windows).  (With eleven launches per
-   * block and the double transform the chain had gained nothing at either rate: profiles/r03z_*.) */
-  int pipeline = a->src.is_dev && !a->src.f;
-  if (getenv("ISEE3_CHAIN_PM_PIPELINE")) pipeline = atoi(getenv("ISEE3_CHAIN_PM_PIPELINE")) != 0;
-  if (pipeline) {
+   * capture that lies in device memory, off for one in host memory or a file (there the next block's staged H2D copy
+   * queues in front of this block's spin-down: 7 % slower; and iq_next would refill a file's one staging buffer while the
+   * previous copy from it may still run).  Measured with six launches per block (profiles/r03ar_*): pmdemod's engine time
+   * 17.8 -> 14-15 ms at 10 MS/s, chain 14.51-14.65 -> 14.72-14.82 Gsamples/s; 5.6 -> 2.3 ms at 250 kS/s, chain the same
+   * (its front end is paced by symdemod's windows).  (With eleven launches per block and the double transform the chain
+   * had gained nothing at either rate: profiles/r03z_*.) */
+  if (a->src.is_dev && !a->src.f) {
     e.fft_peak_begin = pm_peak_begin; e.fft_peak_end = pm_peak_end; e.mix_begin = pm_mix_begin; e.mix_end = pm_mix_end;
   }
   pmdemod_source src = { iq_next, &a->src };
@@ -450,7 +445,6 @@ static void *pm_thread(void *p) {
 static void *sy_thread(void *p) {
   sy_arg *a = p;
   symdemod_engine e = { sy_create, sy_load, sy_ts, sy_demod, sy_destroy, sy_slide, sy_put, sy_scan, sy_window };
-  if (getenv("SYMDEMOD_STEPWISE") && atoi(getenv("SYMDEMOD_STEPWISE"))) e.window = NULL;
   /* this thread writes into the pipe the Viterbi stage reads: should that stage ever go away first, the write must fail
    * with EPIPE (a stage error) and not raise SIGPIPE, whose default action would end the HOST program */
   sigset_t sp;
@@ -508,7 +502,7 @@ static int chain_run(const isee3_chain_opts *co, const iq_src *src, FILE *out) {
   /* how the Viterbi stage takes its symbols.  "progressive": one stream, fed as it arrives, second decoder joining at a
    * cut placed from the expected number of bits (v224hip_progressive_*).  "block": block by block as the reference does,
    * long blocks shared once the front end has finished (bits leave as they are decoded: the form for pipes).  "whole":
-   * wait for all symbols, then split (ISEE3_CHAIN_WHOLE=1; measured 72 vs 57 ms in round 1).  Default: progressive whenever
+   * wait for all symbols, then split (measured 72 vs 57 ms in round 1).  Default: progressive whenever
    * the capture's length is known.  Where the Viterbi decoder is the slower part (250 kS/s) the second decoder joins; where
    * the front end is (10 MS/s) one decoder keeps up with the symbols and the cut is never placed -- and that one decoder
    * still does better than block mode (48 s of 10 MS/s: 40.2 against 45.8 ms): it advances in whole chunks, asynchronously,
@@ -518,7 +512,7 @@ static int chain_run(const isee3_chain_opts *co, const iq_src *src, FILE *out) {
     const double secs = src->iq ? (double)src->nsamples / co->samprate : 0;
     va.expected_bits = (long long)(secs * sa.o.symrate / 2);
     va.progressive = m ? !strcmp(m, "progressive") : va.expected_bits > 0;
-    va.o.whole_input = va.progressive || (m && !strcmp(m, "whole")) || (getenv("ISEE3_CHAIN_WHOLE") && atoi(getenv("ISEE3_CHAIN_WHOLE")));
+    va.o.whole_input = va.progressive || (m && !strcmp(m, "whole"));
   }
   pa.o.quiet = sa.o.quiet = va.o.quiet = !co->verbose;
   pthread_once(&g_chunk_once, chunk_from_env);

@@ -137,8 +137,7 @@ int pmdemod_run_io(const pmdemod_opts *o, const pmdemod_engine *e, const pmdemod
     }
   }
 
-  if (Search_width == 0 && e->fft_peak_begin && e->fft_peak_end && e->mix_begin && e->mix_end &&
-      !(getenv("PMDEMOD_SERIAL") && atoi(getenv("PMDEMOD_SERIAL")))) {
+  if (Search_width == 0 && e->fft_peak_begin && e->fft_peak_end && e->mix_begin && e->mix_end) {
     /* Independent blocks (full-band search, pmdemod.c:273-276: nothing of a block's result enters the next one's search),
        two handles A / B used in turn.  Engine queue: FFT(0) FFT(1) mix(0) FFT(2) mix(1) ... -- block k+1's transform is
        enqueued before block k's peak is waited for, so the engine works while the host forms Quinn's estimate and the

@@ -27,7 +27,6 @@ int main(int argc, char **argv) {
   setlocale(LC_ALL, lang ? lang : "en_US.utf8");
   symdemod_parse_args(&o, argc, argv);
   symdemod_engine e = { eng_create, eng_load, eng_ts, eng_demod, eng_destroy, NULL, NULL, NULL, eng_window };
-  if (getenv("SYMDEMOD_STEPWISE") && atoi(getenv("SYMDEMOD_STEPWISE"))) e.window = NULL;     /* the two-round-trip path */
   if (symdemod_run(&o, &e, 0, stdout, stderr) != 0) {
     fprintf(stderr, "%s: engine failed: %s\n", o.argv0, isee3dsp_last_error());
     return 2;

@@ -60,18 +60,9 @@ extern "C" int isee3dsp_d2h(void *h, const void *d, size_t n) { return hipMemcpy
 // every process and is otherwise idle in this library.  All other streams here are hipStreamNonBlocking, so nothing
 // synchronises with the null stream implicitly; a host application that keeps the null stream busy itself shares it with
 // symdemod's short kernels (correct, slower): ISEE3_CHAIN_SY_NULL=0 then puts both stages on the mode-1 stream.
-// (ISEE3DSP_HIGH_PRIORITY=1 asks for the highest stream priority for created streams; measured: no effect.)
 static thread_local int t_share_stream = 0;
 static hipStream_t g_shared_stream[64];
 extern "C" void isee3dsp_share_stream(int on) { t_share_stream = on; }
-static hipError_t dsp_stream_create_one(hipStream_t *st) {
-  int least = 0, greatest = 0;
-  const char *e = getenv("ISEE3DSP_HIGH_PRIORITY");
-  if (e && atoi(e) && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest < least &&
-      hipStreamCreateWithPriority(st, hipStreamNonBlocking, greatest) == hipSuccess) return hipSuccess;
-  (void)hipGetLastError();
-  return hipStreamCreateWithFlags(st, hipStreamNonBlocking);
-}
 static hipError_t dsp_stream_create(hipStream_t *st, int *owned) {
   int dev = 0;
   *owned = 1;
@@ -79,10 +70,10 @@ static hipError_t dsp_stream_create(hipStream_t *st, int *owned) {
   if (t_share_stream && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
     static std::mutex mu;
     std::lock_guard<std::mutex> lk(mu);
-    if (!g_shared_stream[dev] && dsp_stream_create_one(&g_shared_stream[dev]) != hipSuccess) g_shared_stream[dev] = nullptr;
+    if (!g_shared_stream[dev] && hipStreamCreateWithFlags(&g_shared_stream[dev], hipStreamNonBlocking) != hipSuccess) g_shared_stream[dev] = nullptr;
     if (g_shared_stream[dev]) { *st = g_shared_stream[dev]; *owned = 0; return hipSuccess; }
   }
-  return dsp_stream_create_one(st);
+  return hipStreamCreateWithFlags(st, hipStreamNonBlocking);
 }
 
 static int grow(void **p, size_t *cap, size_t need) {
@@ -552,10 +543,9 @@ extern "C" int symd_load(void *p, const int16_t *samples, int n, int is_dev) {
   if (symd_store_put(p, 0, samples, n, is_dev) != 0) return -1;
   return symd_store_scan(p, n);
 }
-// the ordered timing search: four waves per 64 offsets where it applies (ISEE3DSP_TS1=1: the one-wave kernel)
+// the ordered timing search: four waves per 64 offsets where it applies (symbolclocks == 1), else one wave
 static int launch_ordered_search(Symd *h, int lo, const int *d_sw, int symbolclocks, int nsymbols, int noff, double *d_en) {
-  static const bool one_wave = getenv("ISEE3DSP_TS1") && atoi(getenv("ISEE3DSP_TS1")) != 0;
-  if (symbolclocks == 1 && !one_wave) {
+  if (symbolclocks == 1) {
     const size_t lds = sizeof(double) * 4 * TS4_SYMS * 64;
     static std::atomic<unsigned long long> attr_set{0};
     const unsigned long long bit = 1ull << (h->dev & 63);
@@ -592,7 +582,7 @@ extern "C" int symd_timesearch(void *p, int lo, const int *sw, int symbolclocks,
     unsigned flag = 1;
     // the exact-integer parallel form first -- unless the previous window already left its range (it then will again:
     // at 10 MS/s one symbol spans 9 760 samples and the window total passes 2^53)
-    if (!getenv("ISEE3DSP_SEQUENTIAL") && !h->inexact_last && grow(&h->d_part, &h->part_cap, sizeof(unsigned long long) * (size_t)nslices * (size_t)noff) == 0) {
+    if (!h->inexact_last && grow(&h->d_part, &h->part_cap, sizeof(unsigned long long) * (size_t)nslices * (size_t)noff) == 0) {
       CHK(hipMemsetAsync(h->d_flag, 0, sizeof(unsigned), h->st));
       k_timesearch_part<<<dim3((noff + 255) / 256, nslices), 256, 0, h->st>>>(h->d_P, lo, (const int *)h->d_idx, symbolclocks,
                                                                             nsymbols, noff, (unsigned long long *)h->d_part, h->d_flag);
@@ -604,7 +594,7 @@ extern "C" int symd_timesearch(void *p, int lo, const int *sw, int symbolclocks,
     }
     // remember it for the next windows, and look again every 32nd (a capture may change level)
     h->inexact_last = flag ? (h->inexact_last % 32) + 1 : 0;
-    if (h->inexact_last == 32 || getenv("ISEE3DSP_RETRY_EXACT")) h->inexact_last = 0;
+    if (h->inexact_last == 32) h->inexact_last = 0;
     if (flag) {     // some sum left the exactly-representable range: the reference's own order of additions
       if (launch_ordered_search(h, lo, (const int *)h->d_idx, symbolclocks, nsymbols, noff, (double *)h->pin_e.d) != 0) goto fail;
       CHK(hipGetLastError());
@@ -644,7 +634,7 @@ extern "C" int symd_demod(void *p, const int *edges, int symbolclocks, int nsymb
     CHK(hipGetLastError());
     CHK(hipStreamSynchronize(h->st));
     if (energy_sum) {
-      if (*(volatile unsigned *)((char *)h->pin_hdr.h + 8) || getenv("ISEE3DSP_SEQUENTIAL")) {
+      if (*(volatile unsigned *)((char *)h->pin_hdr.h + 8)) {
         k_seq_energy<<<1, 256, 0, h->st>>>((const long long *)h->d_sym, nsymbols, d_esum);
         CHK(hipStreamSynchronize(h->st));
       }
@@ -748,7 +738,7 @@ extern "C" int symd_window(void *p, int firstsample, const int *sw, int symbolcl
     WinHdr *host_hdr_d = (WinHdr *)((char *)h->pin_hdr.d + 64);
     volatile WinHdr *host_hdr = (volatile WinHdr *)((char *)h->pin_hdr.h + 64);
     const int nslices = (nsymbols + TS_SLICE - 1) / TS_SLICE;
-    const bool exact_form = !getenv("ISEE3DSP_SEQUENTIAL") && !h->inexact_last &&
+    const bool exact_form = !h->inexact_last &&
                             grow(&h->d_part, &h->part_cap, sizeof(unsigned long long) * (size_t)nslices * (size_t)noff) == 0;
     if (exact_form) {
       CHK(hipMemsetAsync(h->d_flag, 0, sizeof(unsigned), h->st));
@@ -763,7 +753,7 @@ extern "C" int symd_window(void *p, int firstsample, const int *sw, int symbolcl
     const unsigned flag = exact_form ? host_hdr->inexact : 1u;
     // the same bookkeeping as symd_timesearch: remember a window that left the exact range, look again every 32nd
     h->inexact_last = flag ? (h->inexact_last % 32) + 1 : 0;
-    if (h->inexact_last == 32 || getenv("ISEE3DSP_RETRY_EXACT")) h->inexact_last = 0;
+    if (h->inexact_last == 32) h->inexact_last = 0;
     if (exact_form && flag) return 1;                               // the ordered kernel has to redo the search
     if (host_hdr->miss || host_hdr->bi < 0) return 1;
     const double best = host_hdr->best, me = best / nsymbols, gain = 100. / sqrt(me);
@@ -1562,11 +1552,6 @@ static int launch_pass(const FftCtx &c, const FftSrc &in, V *dst, int s, PeakAsk
   constexpr int R1 = PassShape<LG>::R1, R2 = PassShape<LG>::R2, R = R1 * R2, TH = FTC * (R1 > R2 ? R1 : R2);
   size_t lds = sizeof(V) * (FIRST ? R + 1 : R) * FTC;                  // a first stage re-uses the tile as its padded output image
   if (PEAK && lds < 512) lds = 512;                                    // (the peak records of the waves)
-  // ISEE3DSP_FFT_LDS_KB=n: every pass ASKS for n KiB of LDS (it uses what it needs).  With 88 exactly one FFT workgroup fits a
-  // CU and 72 KiB stay free: a Viterbi workgroup (68.6 KiB) always finds room beside it, whereas two 64 KiB FFT workgroups
-  // on a CU make the 256-workgroup ACS launch wait for one of them to finish
-  static const size_t lds_floor = getenv("ISEE3DSP_FFT_LDS_KB") ? (size_t)atoi(getenv("ISEE3DSP_FFT_LDS_KB")) * 1024u : 0u;
-  if (lds < lds_floor && lds_floor <= 160u * 1024u) lds = lds_floor;
   // 64 KiB of dynamic LDS at R = 256: raised once per device and instantiation (bit d = done on device d; transforms run
   // from several host threads, a doubled call is harmless, the flag itself is atomic)
   static std::atomic<unsigned long long> attr_set{0};
@@ -1622,10 +1607,8 @@ static int fft_forward(const FftCtx &c, const FftSrc &in, V *out, V *tmp, PeakAs
   int s = 1;
   if (pk) pk->nparts = 0;
   for (int i = 0; i < npass; i++) {
-    // the larger radices first (2^23 = 8 + 8 + 7).  ISEE3DSP_FFT_ORDER=asc puts the smaller ones first (7 + 8 + 8: the first
-    // pass then takes 32 columns = 128-byte read runs): measured at 2^23, 102 + 72 + 67 us against 98 + 73 + 60
-    static const bool asc = getenv("ISEE3DSP_FFT_ORDER") && getenv("ISEE3DSP_FFT_ORDER")[0] == 'a';
-    const int lg = base + ((asc ? i >= npass - extra : i < extra) ? 1 : 0);
+    // the larger radices first (2^23 = 8 + 8 + 7; smaller first measured slower at 2^23: 102 + 72 + 67 us against 98 + 73 + 60)
+    const int lg = base + (i < extra ? 1 : 0);
     V *dst = ((npass - 1 - i) & 1) == 0 ? out : tmp;
     if (pk && i == npass - 1 && i > 0) { if (launch_pass_lg<SRC_C2, false, true, V>(c, lg, cur, dst, s, pk) != 0) return -1; }
     else if ((i == 0 ? launch_pass_lg<SRC, true, false, V>(c, lg, cur, dst, s) : launch_pass_lg<SRC_C2, false, false, V>(c, lg, cur, dst, s)) != 0) return -1;
@@ -1664,7 +1647,7 @@ extern "C" void *pmd_create(int fftsize) {
   if (pin_grow(&h->pin_hdr, PIN_BYTES) != 0) { snprintf(g_err, sizeof g_err, "pmd_create: pinned mailbox"); goto fail; }
   CHK(hipEventCreateWithFlags(&h->ev_peak, hipEventDisableTiming));
   CHK(hipEventCreateWithFlags(&h->ev_mix, hipEventDisableTiming));
-  if (lg >= 12 && !getenv("ISEE3DSP_FFT_REGISTER_RADIX")) {
+  if (lg >= 12) {
     FftCtx c;
     if (fft_tables(&c, fftsize, &h->twA, &h->twB, &h->twR, h->st) != 0) { snprintf(g_err, sizeof g_err, "pmd_create: twiddle tables"); goto fail; }
   } else {                                           // small transforms: register-radix stages on a double copy of the block
@@ -1796,18 +1779,15 @@ static int peak_begin(Pmd *h, int firstbin, int lastbin, bool search) {
       // LDS-staged passes, the first one straight from the int16 block, the last one leaving the peak records
       const FftCtx c{h->N, h->logN, h->twA, h->twB, h->twR, h->st};
       const FftSrc in{nullptr, h->cur_iq, h->have_lo ? h->lo : nullptr, h->cur_flip};
-      const bool ride = !getenv("ISEE3DSP_PEAK_SEPARATE") && grow(&h->d_peakpart, &h->peakpart_cap, sizeof(PeakRec) * (size_t)(h->N / 32 / FT)) == 0;
+      const bool ride = grow(&h->d_peakpart, &h->peakpart_cap, sizeof(PeakRec) * (size_t)(h->N / 32 / FT)) == 0;
       ask.part = (PeakRec *)h->d_peakpart;
       if (fft_forward<SRC_IQ>(c, in, h->spec, h->tmp, ride ? &ask : nullptr) != 0) { snprintf(g_err, sizeof g_err, "pmd_fft_peak: FFT launch failed"); return -1; }
     } else {
       // stages ping-pong so that the last one lands in spec; buf is never written.  Radix plan: the
       // small remainder radix first (its short output runs matter least while s is tiny), then radix 16.
       int radices[12], nst = 0, rem = h->logN;
-      if (getenv("ISEE3DSP_FFT_RADIX2")) { while (rem > 0) { radices[nst++] = 2; rem--; } }
-      else {
-        if (rem % 4) { radices[nst++] = 1 << (rem % 4); rem -= rem % 4; }
-        while (rem > 0) { radices[nst++] = 16; rem -= 4; }
-      }
+      if (rem % 4) { radices[nst++] = 1 << (rem % 4); rem -= rem % 4; }
+      while (rem > 0) { radices[nst++] = 16; rem -= 4; }
       const double2 *src = h->buf;
       int s = 1;
       for (int st = 0; st < nst; st++) {
@@ -1835,7 +1815,7 @@ static int peak_begin(Pmd *h, int firstbin, int lastbin, bool search) {
 fail:
   return -1;
 }
-// 0 enqueued (pmd_mix_end collects); 1 this block takes the synchronous call (small or unaligned, ISEE3DSP_CARRIER_CLOSED=1)
+// 0 enqueued (pmd_mix_end collects); 1 this block takes the synchronous call (small or unaligned)
 extern "C" int pmd_mix_begin(void *p, double cstep, int16_t *out16, double *pre, int out_is_dev) {
   Pmd *h = (Pmd *)p;
   if (!h) return -1;
@@ -1847,8 +1827,7 @@ extern "C" int pmd_mix_begin(void *p, double cstep, int16_t *out16, double *pre,
     const double2 *lo = h->have_lo ? h->lo : nullptr;
     int16_t *o16v = (out16 && out_is_dev) ? out16 : h->d_out16;
     double *oprev = pre ? (out_is_dev ? pre : h->d_pre) : nullptr;
-    static const bool closed_form = getenv("ISEE3DSP_CARRIER_CLOSED") && atoi(getenv("ISEE3DSP_CARRIER_CLOSED")) != 0;
-    if (closed_form || h->N < 1024 || ((uintptr_t)iq & 15u) != 0 || ((uintptr_t)o16v & 7u) != 0 || ((uintptr_t)oprev & 15u) != 0) return 1;
+    if (h->N < 1024 || ((uintptr_t)iq & 15u) != 0 || ((uintptr_t)o16v & 7u) != 0 || ((uintptr_t)oprev & 15u) != 0) return 1;
     uint64_t u_hi, u_lo; double logrho;
     pmd_carrier_params(cstep, &u_hi, &u_lo, &logrho);
     // stepped carrier, four samples per thread and step, both passes and their sums without a host round trip in between
@@ -1897,7 +1876,7 @@ extern "C" int pmd_mix_quantise(void *p, double cstep, pmd_mix *res, int16_t *ou
     const short2 *iq = (const short2 *)h->cur_iq;
     const double2 *lo = h->have_lo ? h->lo : nullptr;
     int nb = (h->N + 255) / 256; if (nb > RED_BLOCKS) nb = RED_BLOCKS;
-    // closed-form carrier per sample (small or unaligned blocks; ISEE3DSP_CARRIER_CLOSED=1)
+    // closed-form carrier per sample (small or unaligned blocks)
     k_mix<<<nb, 256, 0, h->st>>>(iq, lo, h->cur_flip, h->N, u_hi, u_lo, logrho, part);
     k_sum2<<<1, 256, 0, h->st>>>(part, nb, (double2 *)((char *)h->pin_hdr.d + 128));
     double2 dc;

@@ -89,29 +89,15 @@ __device__ __forceinline__ void fused_bflies(v2u16 (&r)[1 << K], unsigned (&acc)
 typedef unsigned v4u32 __attribute__((ext_vector_type(4)));
 typedef unsigned v2u32 __attribute__((ext_vector_type(2)));
 
-// 16-byte store with an explicit cache policy (CP = buffer aux bits: 2 = nt, 16 = sc1 write-through,
-// 17 = sc0 sc1).  Write-through keeps the launch from leaving ~21 MiB dirty in the XCD L2s, which the
-// kernel boundary would otherwise have to flush before the next (dependent) launch can start.
-template <int CP>
-__device__ __forceinline__ void store16(uint32_t *base, size_t bytes, unsigned off_bytes, v4u32 v) {
-  if constexpr (CP == 0) {
-    *reinterpret_cast<v4u32 *>(reinterpret_cast<char *>(base) + off_bytes) = v;
-  } else {
-    __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)bytes, 0x00020000);
-    __builtin_amdgcn_raw_buffer_store_b128(v, rs, (int)off_bytes, 0, CP);
-  }
+// plain 16- / 8-byte stores at a 32-bit byte offset from base
+__device__ __forceinline__ void store16(uint32_t *base, unsigned off_bytes, v4u32 v) {
+  *reinterpret_cast<v4u32 *>(reinterpret_cast<char *>(base) + off_bytes) = v;
 }
-template <int CP>
-__device__ __forceinline__ void store8(uint32_t *base, size_t bytes, unsigned off_bytes, v2u32 v) {
-  if constexpr (CP == 0) {
-    *reinterpret_cast<v2u32 *>(reinterpret_cast<char *>(base) + off_bytes) = v;
-  } else {
-    __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)bytes, 0x00020000);
-    __builtin_amdgcn_raw_buffer_store_b64(v, rs, (int)off_bytes, 0, CP);
-  }
+__device__ __forceinline__ void store8(uint32_t *base, unsigned off_bytes, v2u32 v) {
+  *reinterpret_cast<v2u32 *>(reinterpret_cast<char *>(base) + off_bytes) = v;
 }
 
-template <int K, int T, int CP>
+template <int K, int T>
 __device__ __forceinline__ void fused_stage(v2u16 (&r)[1 << K], const unsigned tid,
                                             const uint8_t *__restrict__ syms,
                                             uint32_t *__restrict__ row) {
@@ -139,11 +125,11 @@ __device__ __forceinline__ void fused_stage(v2u16 (&r)[1 << K], const unsigned t
 #pragma unroll
     for (int g = 0; g < NW; g += 4) {
       v4u32 v = { acc[g], acc[g + 1], acc[g + 2], acc[g + 3] };
-      store16<CP>(row, V224_ROWWORDS * 4, (tid * NW + g) * 4, v);
+      store16(row, (tid * NW + g) * 4, v);
     }
   } else if constexpr (K == 5) {
     v2u32 v = { acc[0], acc[1] };
-    store8<CP>(row, V224_ROWWORDS * 4, tid * 8, v);
+    store8(row, tid * 8, v);
   } else if constexpr (K == 4) {
     row[tid] = acc[0];
   } else if constexpr (K == 3) {
@@ -153,18 +139,15 @@ __device__ __forceinline__ void fused_stage(v2u16 (&r)[1 << K], const unsigned t
   }
 }
 
-template <int K, int CP, int... T>
+template <int K, int... T>
 __device__ __forceinline__ void fused_stages(v2u16 (&r)[1 << K], const unsigned tid,
                                              const uint8_t *__restrict__ syms,
                                              uint32_t *__restrict__ rows, int row0,
                                              std::integer_sequence<int, T...>) {
-  (fused_stage<K, T, CP>(r, tid, syms, rows + (size_t)(row0 + T) * V224_ROWWORDS), ...);
+  (fused_stage<K, T>(r, tid, syms, rows + (size_t)(row0 + T) * V224_ROWWORDS), ...);
 }
 
-#ifndef FUSED_ABLATE
-#define FUSED_ABLATE 0
-#endif
-template <int K, int CP = 0, int CPD = CP, int ABL = FUSED_ABLATE>
+template <int K>
 __global__ __launch_bounds__(256) void k_acs_fused(const uint32_t *__restrict__ oldm,
                                                    uint32_t *__restrict__ newm,
                                                    uint32_t *__restrict__ rows, int row0,
@@ -177,7 +160,7 @@ __global__ __launch_bounds__(256) void k_acs_fused(const uint32_t *__restrict__ 
   {
     const uint32_t *src = oldm + tid;                           // old[(q << XB) + 2*tid .. +1]
 #pragma unroll
-    for (int q = 0; q < NQ; q++) r[q] = (ABL == 2) ? as_v2(tid * 2654435761u + q) : as_v2(src[(size_t)q << (XB - 1)]);
+    for (int q = 0; q < NQ; q++) r[q] = as_v2(src[(size_t)q << (XB - 1)]);
   }
   // the metric loads above are in flight while the workgroup reduces last launch's minima
   const unsigned adj = input_min(ds, pass) - V224_BASE;
@@ -185,55 +168,35 @@ __global__ __launch_bounds__(256) void k_acs_fused(const uint32_t *__restrict__ 
 #pragma unroll
   for (int q = 0; q < NQ; q++) r[q] -= adj2;
 
-  if constexpr (ABL == 1) {       // memory only: same loads and stores, no trellis arithmetic
-#pragma unroll
-    for (int t = 0; t < K; t++) {
-      uint32_t *row = rows + (size_t)(row0 + t) * V224_ROWWORDS;
-      if constexpr (K >= 6) {
-        constexpr int NW = FusedCfg<K>::NW;
-#pragma unroll
-        for (int g = 0; g < NW; g += 4) store16<CPD>(row, V224_ROWWORDS * 4, (tid * NW + g) * 4, v4u32{ as_u32(r[g]), as_u32(r[g + 1]), as_u32(r[g + 2]), as_u32(r[t]) });
-      } else if constexpr (K == 5) store8<CPD>(row, V224_ROWWORDS * 4, tid * 8, v2u32{ as_u32(r[t]), as_u32(r[t + 8]) });
-      else row[tid] = as_u32(r[t]);
-    }
-  } else {
-    fused_stages<K, CPD>(r, tid, syms, rows, row0, std::make_integer_sequence<int, K>{});
-  }
+  fused_stages<K>(r, tid, syms, rows, row0, std::make_integer_sequence<int, K>{});
 
   // write new[(x << K) + q]: lo halves of r[0..NQ) then hi halves, 4*NQ contiguous bytes per thread
   v2u16 mnv = r[0];
 #pragma unroll
   for (int q = 1; q < NQ; q++) mnv = __builtin_elementwise_min(mnv, r[q]);
-  if constexpr (ABL == 2) {       // compute only: one dword out so nothing is dead
-    unsigned x = 0;
+  uint32_t *dst = newm + (size_t)tid * NQ;
+  if constexpr (NQ >= 8) {
 #pragma unroll
-    for (int q = 0; q < NQ; q++) x ^= as_u32(r[q]);
-    if (x == 0x12345678u) newm[tid] = x;
-  } else {
-    uint32_t *dst = newm + (size_t)tid * NQ;
-    if constexpr (NQ >= 8) {
-#pragma unroll
-      for (int q = 0; q < NQ; q += 8) {
-        uint4 lo, hi;
-        lo.x = __builtin_amdgcn_perm(as_u32(r[q + 1]), as_u32(r[q + 0]), 0x05040100u);
-        lo.y = __builtin_amdgcn_perm(as_u32(r[q + 3]), as_u32(r[q + 2]), 0x05040100u);
-        lo.z = __builtin_amdgcn_perm(as_u32(r[q + 5]), as_u32(r[q + 4]), 0x05040100u);
-        lo.w = __builtin_amdgcn_perm(as_u32(r[q + 7]), as_u32(r[q + 6]), 0x05040100u);
-        hi.x = __builtin_amdgcn_perm(as_u32(r[q + 1]), as_u32(r[q + 0]), 0x07060302u);
-        hi.y = __builtin_amdgcn_perm(as_u32(r[q + 3]), as_u32(r[q + 2]), 0x07060302u);
-        hi.z = __builtin_amdgcn_perm(as_u32(r[q + 5]), as_u32(r[q + 4]), 0x07060302u);
-        hi.w = __builtin_amdgcn_perm(as_u32(r[q + 7]), as_u32(r[q + 6]), 0x07060302u);
-        store16<CP>(newm, (size_t)V224_NSTATES * 2, (tid * NQ + (q >> 1)) * 4, v4u32{ lo.x, lo.y, lo.z, lo.w });
-        store16<CP>(newm, (size_t)V224_NSTATES * 2, (tid * NQ + (NQ >> 1) + (q >> 1)) * 4, v4u32{ hi.x, hi.y, hi.z, hi.w });
-      }
-    } else {   // K == 2: 4 slots -> 2 dwords per half
-      uint4 v;
-      v.x = __builtin_amdgcn_perm(as_u32(r[1]), as_u32(r[0]), 0x05040100u);
-      v.y = __builtin_amdgcn_perm(as_u32(r[3]), as_u32(r[2]), 0x05040100u);
-      v.z = __builtin_amdgcn_perm(as_u32(r[1]), as_u32(r[0]), 0x07060302u);
-      v.w = __builtin_amdgcn_perm(as_u32(r[3]), as_u32(r[2]), 0x07060302u);
-      reinterpret_cast<uint4 *>(dst)[0] = v;
+    for (int q = 0; q < NQ; q += 8) {
+      uint4 lo, hi;
+      lo.x = __builtin_amdgcn_perm(as_u32(r[q + 1]), as_u32(r[q + 0]), 0x05040100u);
+      lo.y = __builtin_amdgcn_perm(as_u32(r[q + 3]), as_u32(r[q + 2]), 0x05040100u);
+      lo.z = __builtin_amdgcn_perm(as_u32(r[q + 5]), as_u32(r[q + 4]), 0x05040100u);
+      lo.w = __builtin_amdgcn_perm(as_u32(r[q + 7]), as_u32(r[q + 6]), 0x05040100u);
+      hi.x = __builtin_amdgcn_perm(as_u32(r[q + 1]), as_u32(r[q + 0]), 0x07060302u);
+      hi.y = __builtin_amdgcn_perm(as_u32(r[q + 3]), as_u32(r[q + 2]), 0x07060302u);
+      hi.z = __builtin_amdgcn_perm(as_u32(r[q + 5]), as_u32(r[q + 4]), 0x07060302u);
+      hi.w = __builtin_amdgcn_perm(as_u32(r[q + 7]), as_u32(r[q + 6]), 0x07060302u);
+      store16(newm, (tid * NQ + (q >> 1)) * 4, v4u32{ lo.x, lo.y, lo.z, lo.w });
+      store16(newm, (tid * NQ + (NQ >> 1) + (q >> 1)) * 4, v4u32{ hi.x, hi.y, hi.z, hi.w });
     }
+  } else {   // K == 2: 4 slots -> 2 dwords per half
+    uint4 v;
+    v.x = __builtin_amdgcn_perm(as_u32(r[1]), as_u32(r[0]), 0x05040100u);
+    v.y = __builtin_amdgcn_perm(as_u32(r[3]), as_u32(r[2]), 0x05040100u);
+    v.z = __builtin_amdgcn_perm(as_u32(r[1]), as_u32(r[0]), 0x07060302u);
+    v.w = __builtin_amdgcn_perm(as_u32(r[3]), as_u32(r[2]), 0x07060302u);
+    reinterpret_cast<uint4 *>(dst)[0] = v;
   }
 
   unsigned mn = (unsigned)mnv.x < (unsigned)mnv.y ? (unsigned)mnv.x : (unsigned)mnv.y;

@@ -28,7 +28,7 @@
 //           back for anything that needs the natural order.
 //
 // Beyond the reference's nine functions (include/viterbi224_hip.h): block streaming decode with the tracebacks
-// on a second stream, a batch of independent frames over several decoders, and ONE stream decoded by several
+// in the decoder's own stream, a batch of independent frames over several decoders, and ONE stream decoded by several
 // decoders at once whose seams are verified (equal path metrics up to a constant => identical continuation).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -60,8 +60,7 @@ struct EvPair { hipEvent_t a, b; unsigned steps, launches; };
 
 struct V224 {
   int len, engine, K, dev;
-  hipStream_t st;           // ACS stream
-  hipStream_t st2;          // traceback stream: == st by default, an own stream with V224HIP_TB_STREAM=1 (tb_own_stream())
+  hipStream_t st;           // the decoder's one stream: passes and tracebacks (see "Where a decoder's tracebacks run")
   uint16_t *m[2];
   int cur;                  // index of the "old" metric buffer
   uint32_t *rows;           // len x 2^18 dwords
@@ -83,7 +82,7 @@ struct V224 {
   unsigned long long launches_seen;
   std::vector<EvPair> ev_busy, ev_free;
   unsigned long long prof_launches, prof_steps; double prof_ms;
-  hipEvent_t ev_acs[2], ev_tb[2];
+  hipEvent_t ev_staged;     // decode_frames: the other decoders wait for the symbols decoder 0 stages
   // kept between calls (grow-only, freed by delete): seam snapshots of stream_decode_split ([0] as the earlier decoder
   // "A" of a seam, [1] as the later one "B"), their events, the warm-up output nobody reads
   uint16_t *snap[2]; hipEvent_t ev_snap[2];
@@ -101,12 +100,10 @@ static std::atomic<int> g_device{-1};
 // scratch/pipe_scan.py: a decoder whose traceback stream is the 4th queue after its pass stream: 1.66 -> 0.62 Msymbols/s;
 // two decoders with own traceback streams and one foreign queue between them: 2.44 -> 1.67; the chain 35 -> 57 ms --
 // all depending on how many streams the process had created and destroyed before).  A decoder with a pass stream AND a
-// traceback stream needs two pipes, two of them all four, and nobody controls which queue gets which.  So by default a
+// traceback stream needs two pipes, two of them all four, and nobody controls which queue gets which.  So a
 // decoder has ONE stream: the tracebacks of a chunk run in it, behind the chunk's passes, with the wave-per-bit
 // kernel k_decodebits_spec (~35 us per chunk of any size; another decoder's passes fill the GPU meanwhile).  Two
 // decoders then need two pipes, the whole chain four (two decoders, pmdemod, symdemod).
-// V224HIP_TB_STREAM=1 gives every decoder its own traceback stream again (tracebacks under the next chunk's passes).
-static bool tb_own_stream(void) { const char *e = getenv("V224HIP_TB_STREAM"); return e && atoi(e) != 0; }
 
 extern "C" int v224hip_device_count(void) {
   int n = 0;
@@ -581,7 +578,7 @@ static int env_int(const char *name, int dflt) {
 // write burst at the end of an LDS15 pass drains: allocations fall into two classes, a pair from the same class
 // runs the memory phases of a pass in ~8.8 us, a mixed pair in ~11.5 us (scratch/l15_pairs.hip; which class an
 // allocation lands in varies from process to process).  So: time the pass with its arithmetic compiled out
-// (template ABL = 1: same loads, LDS traffic and stores) on a few candidate partners for m[0], keep the fastest.
+// (template NOARITH: same loads, LDS traffic and stores) on a few candidate partners for m[0], keep the fastest.
 static int place_metrics(V224 *v) {
   const int NCAND = 6, NWARM = 4, NPROBE = 12;
   uint16_t *cand[NCAND] = {v->m[1], nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -596,8 +593,8 @@ static int place_metrics(V224 *v) {
     uint16_t *m[2] = {v->m[0], cand[c]};
     for (int i = -NWARM; i < NPROBE; i++) {
       if (i == 0) HIPCHK(hipEventRecord(a, v->st));
-      if (i & 1) k_acs_lds15<1, false, true><<<256, 1024, L15_LDS_BYTES, v->st>>>(m[1], m[0], v->rows, 0, v->len, v->dmisc, v->ds, (unsigned)i, v->rowmeta);
-      else       k_acs_lds15<1, true, false><<<256, 1024, L15_LDS_BYTES, v->st>>>(m[0], m[1], v->rows, 0, v->len, v->dmisc, v->ds, (unsigned)i, v->rowmeta);
+      if (i & 1) k_acs_lds15<true, false, true><<<256, 1024, L15_LDS_BYTES, v->st>>>(m[1], m[0], v->rows, 0, v->len, v->dmisc, v->ds, (unsigned)i, v->rowmeta);
+      else       k_acs_lds15<true, true, false><<<256, 1024, L15_LDS_BYTES, v->st>>>(m[0], m[1], v->rows, 0, v->len, v->dmisc, v->ds, (unsigned)i, v->rowmeta);
     }
     HIPCHK(hipEventRecord(b, v->st));
     HIPCHK(hipEventSynchronize(b));
@@ -642,11 +639,11 @@ extern "C" void *v224hip_create(int len, int engine, int k) {
   if (v->K < 1) v->K = 1;
   if (v->K > FUSED_MAX_K) v->K = FUSED_MAX_K;
   { int gd = g_device.load(std::memory_order_acquire); v->dev = gd >= 0 ? gd : env_int("V224HIP_DEVICE", 0); }
-  // whole passes per chunk (1020 = 68 x 15).  With the tracebacks in the pass stream a chunk costs ~35 us of traceback
-  // latency whatever its size, and the ring only has to hold delay + ONE chunk: the default doubles at equal memory.
-  v->chunk = env_int("V224HIP_CHUNK", v->engine == V224HIP_ENGINE_LDS ? 1024 : (tb_own_stream() ? 1020 : 2040));
+  // whole passes per chunk (2040 = 136 x 15).  With the tracebacks in the pass stream a chunk costs ~35 us of traceback
+  // latency whatever its size, and the ring only has to hold delay + ONE chunk.
+  v->chunk = env_int("V224HIP_CHUNK", v->engine == V224HIP_ENGINE_LDS ? 1024 : 2040);
   HIPCHK(hipSetDevice(v->dev));
-  if (v->engine == V224HIP_ENGINE_LDS15) {       // 133 KiB of dynamic LDS per workgroup: above the default cap
+  if (v->engine == V224HIP_ENGINE_LDS15) {       // 68.6 KiB of dynamic LDS per workgroup: above the default cap
     // the per-thread parity table of the 15-step kernel, once per device; decoders are created from several threads at
     // once (chain stages, segment workers): the flag and the upload are under one lock
     static std::mutex tab_mu;
@@ -660,28 +657,13 @@ extern "C" void *v224hip_create(int len, int engine, int k) {
         tab_done[v->dev] = true;
       }
     }
-    HIPCHK(hipFuncSetAttribute((const void *)k_acs_lds15<0, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, L15_LDS_BYTES));
-    HIPCHK(hipFuncSetAttribute((const void *)k_acs_lds15<0, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, L15_LDS_BYTES));
-    HIPCHK(hipFuncSetAttribute((const void *)k_acs_lds15<0, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, L15_LDS_BYTES));
-    HIPCHK(hipFuncSetAttribute((const void *)k_acs_lds15<1, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, L15_LDS_BYTES));
-    HIPCHK(hipFuncSetAttribute((const void *)k_acs_lds15<1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, L15_LDS_BYTES));
+    HIPCHK(hipFuncSetAttribute((const void *)k_acs_lds15<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, L15_LDS_BYTES));
+    HIPCHK(hipFuncSetAttribute((const void *)k_acs_lds15<false, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, L15_LDS_BYTES));
+    HIPCHK(hipFuncSetAttribute((const void *)k_acs_lds15<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, L15_LDS_BYTES));
+    HIPCHK(hipFuncSetAttribute((const void *)k_acs_lds15<true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, L15_LDS_BYTES));
+    HIPCHK(hipFuncSetAttribute((const void *)k_acs_lds15<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, L15_LDS_BYTES));
   }
-  {
-    // V224HIP_STREAM_PRIORITY=low|high: the decoder's stream at the lowest / highest priority the device offers (default:
-    // normal).  An experiment knob: measured in the chain (decoders low and / or front end high), no effect on any stage.
-    const char *pr = getenv("V224HIP_STREAM_PRIORITY");
-    int least = 0, greatest = 0;
-    if (pr && (pr[0] == 'l' || pr[0] == 'h') && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest < least)
-      HIPCHK(hipStreamCreateWithPriority(&v->st, hipStreamNonBlocking, pr[0] == 'l' ? least : greatest));
-    else HIPCHK(hipStreamCreateWithFlags(&v->st, hipStreamNonBlocking));
-  }
-  if (tb_own_stream()) {
-    if (getenv("V224HIP_TEST_GAP")) {      // experiment (scratch/pipe_scan.py): GAP other hardware queues created in between
-      static hipStream_t dummies[64]; static int nd = 0;
-      for (int g = 0; g < atoi(getenv("V224HIP_TEST_GAP")) && nd < 64; g++) HIPCHK(hipStreamCreateWithFlags(&dummies[nd++], hipStreamNonBlocking));
-    }
-    HIPCHK(hipStreamCreateWithFlags(&v->st2, hipStreamNonBlocking));
-  } else v->st2 = v->st;                   // tracebacks in the pass stream
+  HIPCHK(hipStreamCreateWithFlags(&v->st, hipStreamNonBlocking));
   HIPCHK(hipMalloc(&v->m[0], sizeof(uint16_t) * V224_NSTATES));
   HIPCHK(hipMalloc(&v->m[1], sizeof(uint16_t) * V224_NSTATES));
   HIPCHK(hipMalloc(&v->rows, (size_t)len * V224_ROWWORDS * sizeof(uint32_t)));
@@ -693,10 +675,7 @@ extern "C" void *v224hip_create(int len, int engine, int k) {
   v->dmisc_cap = 1 << 20;
   HIPCHK(hipMalloc(&v->dmisc, v->dmisc_cap));
   HIPCHK(hipMemsetAsync(v->dmisc, 0, 4096, v->st));      // (counters live here: chainback pieces redone at +96)
-  for (int i = 0; i < 2; i++) {
-    HIPCHK(hipEventCreateWithFlags(&v->ev_acs[i], hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&v->ev_tb[i], hipEventDisableTiming));
-  }
+  HIPCHK(hipEventCreateWithFlags(&v->ev_staged, hipEventDisableTiming));
   if (v->engine == V224HIP_ENGINE_LDS15 && len >= 15 && env_int("V224HIP_PLACE", 1) && place_metrics(v) != 0) goto fail;
   if (getenv("V224HIP_VERBOSE"))
     fprintf(stderr, "v224hip: create len %d: m0 %p m1 %p rows %p rowmeta %p ds %p dmisc %p\n", len, (void *)v->m[0], (void *)v->m[1],
@@ -715,25 +694,19 @@ extern "C" void delete_viterbi224(void *p) {
   if (!v) return;
   (void)hipSetDevice(v->dev);
   if (v->st) (void)hipStreamSynchronize(v->st);
-  if (v->st2 && v->st2 != v->st) (void)hipStreamSynchronize(v->st2);
   for (auto &e : v->ev_busy) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
   for (auto &e : v->ev_free) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-  for (int i = 0; i < 2; i++) {
-    if (v->ev_acs[i]) (void)hipEventDestroy(v->ev_acs[i]);
-    if (v->ev_tb[i]) (void)hipEventDestroy(v->ev_tb[i]);
-  }
+  if (v->ev_staged) (void)hipEventDestroy(v->ev_staged);
   (void)hipFree(v->m[0]); (void)hipFree(v->m[1]); (void)hipFree(v->rows); (void)hipFree(v->rowmeta);
   (void)hipFree(v->ds); (void)hipFree(v->dsyms); (void)hipFree(v->dout); (void)hipFree(v->dmisc);
   (void)hipFree(v->snap[0]); (void)hipFree(v->snap[1]); (void)hipFree(v->warmout);
   for (int i = 0; i < 2; i++) if (v->ev_snap[i]) (void)hipEventDestroy(v->ev_snap[i]);
-  if (v->st2 && v->st2 != v->st) (void)hipStreamDestroy(v->st2);
   if (v->st) (void)hipStreamDestroy(v->st);
   delete v;
 }
 
-static int init_enqueue(V224 *v, int starting_state, bool wait_tracebacks) {
+static int init_enqueue(V224 *v, int starting_state) {
   HIPCHK(hipSetDevice(v->dev));
-  if (wait_tracebacks && v->st2 != v->st) HIPCHK(hipStreamSynchronize(v->st2));        // no traceback may still be reading
   v->cur = 0; v->dp = 0; v->nsteps = 0; v->pass = 0; v->min_valid = true;
   v->fresh = true; v->start = (unsigned)starting_state & V224_SMASK;
   // one kernel, straight in the metric order the engine's first pass wants (a fresh buffer in the other order is a
@@ -748,7 +721,7 @@ fail:
 extern "C" int init_viterbi224(void *p, int starting_state) {
   V224 *v = (V224 *)p;
   if (!v) return -1;
-  return init_enqueue(v, starting_state, true);
+  return init_enqueue(v, starting_state);
 }
 
 // ---- profiling helpers -------------------------------------------------------------------
@@ -830,7 +803,7 @@ static int enqueue_acs(V224 *v, const uint8_t *d_syms, int nbits) {
       ensure_layout(v, 1);
       const bool last = (nbits - done - 15) < 15;
       const bool tin = v->min_valid, tout = !tin || last;
-#define LDS15_GO(TIN, TOUT) k_acs_lds15<0, TIN, TOUT><<<256, 1024, L15_LDS_BYTES, v->st>>>(v->m[v->cur], v->m[v->cur ^ 1], \
+#define LDS15_GO(TIN, TOUT) k_acs_lds15<false, TIN, TOUT><<<256, 1024, L15_LDS_BYTES, v->st>>>(v->m[v->cur], v->m[v->cur ^ 1], \
                                v->rows, v->dp, v->len, d_syms + 2 * done, v->ds, v->pass, v->rowmeta)
       if (tin && tout) LDS15_GO(true, true); else if (tin) LDS15_GO(true, false); else LDS15_GO(false, true);
 #undef LDS15_GO
@@ -857,7 +830,7 @@ static int enqueue_acs(V224 *v, const uint8_t *d_syms, int nbits) {
       // (remainder passes, traceback helpers, the next call) finds valid minima.
       const bool last = (nbits - done - 8) < 8;      // next pass is a remainder pass or none
       const bool tin = v->min_valid, tout = !tin || last;
-#define LDS8_GO(TIN, TOUT) k_acs_lds8<0, TIN, TOUT><<<512, 512, 0, v->st>>>(v->m[v->cur], v->m[v->cur ^ 1], v->rows, v->dp, \
+#define LDS8_GO(TIN, TOUT) k_acs_lds8<TIN, TOUT><<<512, 512, 0, v->st>>>(v->m[v->cur], v->m[v->cur ^ 1], v->rows, v->dp, \
                                                    d_syms + 2 * done, v->ds, v->pass, v->rowmeta)
       if (tin && tout) LDS8_GO(true, true); else if (tin) LDS8_GO(true, false); else LDS8_GO(false, true);
 #undef LDS8_GO
@@ -979,15 +952,16 @@ fail:
   return 0;
 }
 
-// framed chainback on stream st: 16 verified pieces at once where the frame is long enough, else the serial walk
-static void launch_chainback(V224 *v, hipStream_t st, unsigned nbits, unsigned endstate, uint8_t *d_out, unsigned row0) {
+// framed chainback from the ring's row 0 on the decoder's stream: 16 verified pieces at once where the frame is long
+// enough, else the serial walk
+static void launch_chainback(V224 *v, unsigned nbits, unsigned endstate, uint8_t *d_out) {
   const int serial = env_int("V224HIP_SERIAL_CHAINBACK", 0);   // 1: one lane, 2: one wave (read per call: tests switch it)
-  if (serial == 1 && row0 == 0) k_chainback<<<1, 64, 0, st>>>(v->rows, v->rowmeta, v->len, nbits, endstate, d_out);
+  if (serial == 1) k_chainback<<<1, 64, 0, v->st>>>(v->rows, v->rowmeta, v->len, nbits, endstate, d_out);
   else if (serial || nbits < CB_MINBITS || nbits > 8u * CB_MAXBYTES)
-    k_chainback_spec<<<1, 64, 0, st>>>(v->rows, v->rowmeta, v->len, nbits, endstate, d_out, row0);
+    k_chainback_spec<<<1, 64, 0, v->st>>>(v->rows, v->rowmeta, v->len, nbits, endstate, d_out, 0u);
   else
-    k_chainback_par<<<1, CB_WAVES * 64, 0, st>>>(v->rows, v->rowmeta, v->len, nbits, endstate, d_out, row0, (unsigned *)(v->dmisc + 96),
-                                                 env_int("V224HIP_CB_WARM", CB_WARM));
+    k_chainback_par<<<1, CB_WAVES * 64, 0, v->st>>>(v->rows, v->rowmeta, v->len, nbits, endstate, d_out, 0u, (unsigned *)(v->dmisc + 96),
+                                                    CB_WARM);
 }
 
 extern "C" int chainback_viterbi224(void *p, unsigned char *data, unsigned int nbits,
@@ -999,7 +973,7 @@ extern "C" int chainback_viterbi224(void *p, unsigned char *data, unsigned int n
     size_t nbytes = (nbits + 7) / 8;
     HIPCHK(hipSetDevice(v->dev));
     if (ensure_cap(&v->dout, &v->dout_cap, nbytes) != 0) return -1;
-    launch_chainback(v, v->st, nbits, endstate, v->dout, 0);
+    launch_chainback(v, nbits, endstate, v->dout);
     // the port writes data[n>>3] only where (n & 7) == 0, i.e. nbits/8 bytes (+1 if ragged)
     HIPCHK(hipMemcpyAsync(data, v->dout, nbytes, hipMemcpyDeviceToHost, v->st));
     HIPCHK(hipStreamSynchronize(v->st));
@@ -1011,8 +985,8 @@ fail:
 
 // ---- batch of independent frames ------------------------------------------------------------
 // Frame f goes to decoder f % ndec; every decoder works on its own stream, so with two decoders one frame's
-// passes run under the other's (two LDS15 workgroups fit a CU) and a frame's traceback runs under the next
-// frame's ACS.  Nothing synchronises with the host until all frames are enqueued.
+// passes run under the other's (two LDS15 workgroups fit a CU) and a frame's traceback runs under the other
+// decoder's next frame.  Nothing synchronises with the host until all frames are enqueued.
 extern "C" int v224hip_decode_frames(void *const *decoders, int ndec, const uint8_t *syms, int nframes,
                                      int framebits, int startstate, unsigned int endstate, uint8_t *out) {
   uint8_t *d_syms = nullptr, *d_out = nullptr;       // = decoder 0's staging buffers
@@ -1033,24 +1007,16 @@ extern "C" int v224hip_decode_frames(void *const *decoders, int ndec, const uint
       }
     }
     HIPCHK(hipSetDevice(v0->dev));
-    // Two things make a batch cheaper when the rings are long enough (len >= 2 * padded frame):
-    //  * a frame is padded with erasures to whole 15-step passes -- steps after the frame's last one cannot change the
-    //    decisions before it, and the traceback starts at the frame's own last row -- so no remainder pass and no
-    //    switch of the metric order;
-    //  * frames of one decoder alternate between the two halves of its ring, and a frame's traceback runs on the
-    //    decoder's second stream under the next frame's passes.
-    bool dual = v0->st2 != v0->st;        // ring halves only pay with an own traceback stream
+    // Where the rings are long enough, a frame is padded with erasures to whole 15-step passes -- steps after the frame's
+    // last one cannot change the decisions before it, and the traceback starts at the frame's own last row -- so no
+    // remainder pass and no switch of the metric order.
     const int padbits = v0->engine == V224HIP_ENGINE_LDS15 ? (framebits + 14) / 15 * 15 : framebits;
-    for (int i = 0; i < ndec; i++) {
-      V224 *v = (V224 *)decoders[i];
-      if (v->len < 2 * padbits || v->engine != v0->engine || v->st2 == v->st) dual = false;
-    }
     bool pad = padbits != framebits;
     for (int i = 0; i < ndec; i++) if (((V224 *)decoders[i])->len < padbits || ((V224 *)decoders[i])->engine != v0->engine) pad = false;
-    const int runbits = (dual || pad) ? padbits : framebits;
+    const int runbits = pad ? padbits : framebits;
     const size_t stride = 2 * (size_t)runbits;
     // staging lives in decoder 0 (grow-only, kept between calls): no hipMalloc / hipFree per batch
-    for (int i = 0; i < ndec; i++) { HIPCHK(hipStreamSynchronize(((V224 *)decoders[i])->st)); HIPCHK(hipStreamSynchronize(((V224 *)decoders[i])->st2)); }
+    for (int i = 0; i < ndec; i++) HIPCHK(hipStreamSynchronize(((V224 *)decoders[i])->st));
     if (ensure_cap(&v0->dsyms, &v0->dsyms_cap, stride * nframes) != 0 || ensure_cap(&v0->dout, &v0->dout_cap, outbytes * nframes) != 0) {
       snprintf(g_err, sizeof g_err, "decode_frames: device staging allocation failed");
       return -1;
@@ -1059,28 +1025,18 @@ extern "C" int v224hip_decode_frames(void *const *decoders, int ndec, const uint
     d_syms = v0->dsyms; d_out = v0->dout;
     if (stride != symbytes) HIPCHK(hipMemsetAsync(d_syms, 128, stride * nframes, v0->st));       // erasures behind every frame
     HIPCHK(hipMemcpy2DAsync(d_syms, stride, syms, symbytes, symbytes, (size_t)nframes, hipMemcpyHostToDevice, v0->st));
-    HIPCHK(hipEventRecord(v0->ev_acs[0], v0->st));
-    for (int i = 1; i < ndec; i++) HIPCHK(hipStreamWaitEvent(((V224 *)decoders[i])->st, v0->ev_acs[0], 0));
+    HIPCHK(hipEventRecord(v0->ev_staged, v0->st));
+    for (int i = 1; i < ndec; i++) HIPCHK(hipStreamWaitEvent(((V224 *)decoders[i])->st, v0->ev_staged, 0));
     for (int f = 0; f < nframes; f++) {
       V224 *v = (V224 *)decoders[f % ndec];
-      const int h = dual ? (f / ndec) & 1 : 0;
-      if (dual && f / ndec >= 2) HIPCHK(hipStreamWaitEvent(v->st, v->ev_tb[h], 0));   // this half's previous traceback is done
-      if (init_enqueue(v, startstate, !dual) != 0) goto fail;
-      v->dp = h * padbits;
+      if (init_enqueue(v, startstate) != 0) goto fail;
       if (enqueue_acs(v, d_syms + stride * f, runbits) != 0) goto fail;
-      if (dual) {
-        HIPCHK(hipEventRecord(v->ev_acs[h], v->st));
-        HIPCHK(hipStreamWaitEvent(v->st2, v->ev_acs[h], 0));
-        launch_chainback(v, v->st2, (unsigned)framebits, endstate, d_out + outbytes * f, (unsigned)(h * padbits));
-        HIPCHK(hipEventRecord(v->ev_tb[h], v->st2));
-      } else if (!getenv("V224HIP_FRAMES_NO_TB"))          // (measurement hook: passes only)
-        launch_chainback(v, v->st, (unsigned)framebits, endstate, d_out + outbytes * f, 0);
+      launch_chainback(v, (unsigned)framebits, endstate, d_out + outbytes * f);
     }
     HIPCHK(hipGetLastError());
     for (int i = 0; i < ndec; i++) {
       V224 *v = (V224 *)decoders[i];
-      if (i > 0) HIPCHK(hipStreamSynchronize(v->st));
-      HIPCHK(hipStreamSynchronize(v->st2));
+      HIPCHK(hipStreamSynchronize(v->st));
       v->dp = 0;                          // the object is left as after a plain init + update: callers re-init anyway
     }
     HIPCHK(hipMemcpyAsync(out, d_out, outbytes * nframes, hipMemcpyDeviceToHost, v0->st));
@@ -1088,7 +1044,7 @@ extern "C" int v224hip_decode_frames(void *const *decoders, int ndec, const uint
   }
   rc = 0;
 fail:
-  if (rc != 0) for (int i = 0; i < ndec; i++) if (decoders[i]) { (void)hipStreamSynchronize(((V224 *)decoders[i])->st); (void)hipStreamSynchronize(((V224 *)decoders[i])->st2); }
+  if (rc != 0) for (int i = 0; i < ndec; i++) if (decoders[i]) (void)hipStreamSynchronize(((V224 *)decoders[i])->st);
   return rc;
 }
 
@@ -1123,53 +1079,27 @@ extern "C" int min_metric_viterbi224(void *p) {
 // ---- streaming block decode -------------------------------------------------------------
 extern "C" int v224hip_stream_chunk(void *p) { return p ? ((V224 *)p)->chunk : -1; }
 
-// ACS of chunk c runs on st; its tracebacks run on st2 while chunk c+1's ACS proceeds.
-// Ring safety: chunk c+2's ACS (which may overwrite rows chunk c's traceback still reads once
-// len < delay + 3*chunk) waits for chunk c's traceback event.
+// One stream: a chunk's passes, then its tracebacks (wave per bit), then the next chunk.  The ring holds delay + one chunk.
 extern "C" int v224hip_stream_decode_dev(void *p, const uint8_t *d_syms, int nbits, int delay,
                                          uint8_t *d_out) {
   V224 *v = (V224 *)p;
   if (!v) return -1;
   if (nbits <= 0) return 0;
-  if (delay <= 0 || v->len < delay + (v->st2 == v->st ? 1 : 2) * v->chunk) {
-    snprintf(g_err, sizeof g_err, "stream_decode: need len >= delay + %d*chunk (len=%d delay=%d chunk=%d)",
-             v->st2 == v->st ? 1 : 2, v->len, delay, v->chunk);
+  if (delay <= 0 || v->len < delay + v->chunk) {
+    snprintf(g_err, sizeof g_err, "stream_decode: need len >= delay + chunk (len=%d delay=%d chunk=%d)",
+             v->len, delay, v->chunk);
     return -1;
   }
   HIPCHK(hipSetDevice(v->dev));
-  if (v->st2 == v->st) {
-    // one stream: the chunk's passes, then its tracebacks (wave per bit), then the next chunk
-    for (int done = 0; done < nbits;) {
-      int n = nbits - done < v->chunk ? nbits - done : v->chunk;
-      int dp_first = (v->dp + 1) % v->len;            // ring index after the chunk's first step
-      unsigned long long steps_first = v->nsteps + 1;
-      if (enqueue_acs(v, d_syms + 2 * (size_t)done, n) != 0) return -1;
-      k_decodebits_spec<<<(n + 3) / 4, 256, 0, v->st>>>(v->rows, v->rowmeta, v->len, dp_first, steps_first, n, delay, 0u, d_out + done);
-      done += n;
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
+  for (int done = 0; done < nbits;) {
+    int n = nbits - done < v->chunk ? nbits - done : v->chunk;
+    int dp_first = (v->dp + 1) % v->len;            // ring index after the chunk's first step
+    unsigned long long steps_first = v->nsteps + 1;
+    if (enqueue_acs(v, d_syms + 2 * (size_t)done, n) != 0) return -1;
+    k_decodebits_spec<<<(n + 3) / 4, 256, 0, v->st>>>(v->rows, v->rowmeta, v->len, dp_first, steps_first, n, delay, 0u, d_out + done);
+    done += n;
   }
-  {
-    int c = 0;
-    for (int done = 0; done < nbits; c++) {
-      int n = nbits - done < v->chunk ? nbits - done : v->chunk;
-      if (c >= 2) HIPCHK(hipStreamWaitEvent(v->st, v->ev_tb[c & 1], 0));
-      int dp_first = (v->dp + 1) % v->len;            // ring index after the chunk's first step
-      unsigned long long steps_first = v->nsteps + 1;
-      if (enqueue_acs(v, d_syms + 2 * (size_t)done, n) != 0) return -1;
-      HIPCHK(hipEventRecord(v->ev_acs[c & 1], v->st));
-      HIPCHK(hipStreamWaitEvent(v->st2, v->ev_acs[c & 1], 0));
-      k_decodebits<<<(n + 63) / 64, 64, 0, v->st2>>>(v->rows, v->rowmeta, v->len, dp_first, steps_first,
-                                                    n, delay, 0u, d_out + done);
-      HIPCHK(hipEventRecord(v->ev_tb[c & 1], v->st2));
-      done += n;
-    }
-    HIPCHK(hipGetLastError());
-    // leave st ordered after the last tracebacks so that later API calls see a quiet ring
-    HIPCHK(hipStreamWaitEvent(v->st, v->ev_tb[(c - 1) & 1], 0));
-    if (c >= 2) HIPCHK(hipStreamWaitEvent(v->st, v->ev_tb[c & 1], 0));
-  }
+  HIPCHK(hipGetLastError());
   return 0;
 fail:
   return -1;
@@ -1211,7 +1141,7 @@ static int split_core(void *const *decoders, int ndec, const uint8_t *d_syms, in
   V224 *v0 = (V224 *)decoders[0];
   for (int j = 0; j < ndec; j++) {
     V224 *v = (V224 *)decoders[j];
-    if (!v || v->dev != v0->dev || v->chunk != v0->chunk || v->len < delay + (v->st2 == v->st ? 1 : 2) * v->chunk) {
+    if (!v || v->dev != v0->dev || v->chunk != v0->chunk || v->len < delay + v->chunk) {
       snprintf(g_err, sizeof g_err, "stream_decode_split: decoder %d is NULL, on another device, has another chunk size or a short ring", j);
       return -1;
     }
@@ -1396,11 +1326,8 @@ static double prog_now(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC
 #define PROG_LOOK 24       /* ... and either decoder afterwards: feed() hands out work for some tens of ms, never the whole backlog */
 #define PROG_SLAB 8        /* chunks per call when both decoders have a backlog: their launches must interleave in the queues */
 
-// share of decoder 0's progress that decoder 1 makes while the symbols' producer still runs on the GPU ($V224HIP_PROG_GAMMA)
-static double prog_gamma(void) {
-  static const double gm = getenv("V224HIP_PROG_GAMMA") ? atof(getenv("V224HIP_PROG_GAMMA")) : 0.33;
-  return gm < -3 ? -3 : gm > 1 ? 1 : gm;
-}
+// share of decoder 0's progress that decoder 1 makes while the symbols' producer still runs on the GPU
+#define PROG_GAMMA 0.33
 static void prog_poll(V224Prog *g, int j) {
   V224Prog::Track &t = g->tr[j];
   while (t.count > 0 && hipEventQuery(t.ev[t.head]) == hipSuccess) {
@@ -1516,7 +1443,7 @@ static int prog_advance(V224Prog *g, bool final) {
         if (dt > 0.05 && g->avail > 0 && g->expected > g->avail && a_done > 0) {
           const double arrival = (double)g->avail / dt, a_rate = (double)a_done / dt;
           const double t_rem = (double)(g->expected - g->avail) / arrival;
-          bias = (long long)((1.0 - prog_gamma()) * a_rate * t_rem / 2.0);
+          bias = (long long)((1.0 - PROG_GAMMA) * a_rate * t_rem / 2.0);
         }
       }
       const long long x0 = (g->expected + g->warm + a_done) / 2 / q * q;          // the even split of what is left
@@ -1559,7 +1486,7 @@ extern "C" void *v224hip_progressive_begin(void *const *decoders, int ndec, long
   V224 *v0 = (V224 *)decoders[0];
   for (int j = 0; j < ndec; j++) {
     V224 *v = (V224 *)decoders[j];
-    if (!v || v->dev != v0->dev || v->chunk != v0->chunk || v->len < delay + (v->st2 == v->st ? 1 : 2) * v->chunk) {
+    if (!v || v->dev != v0->dev || v->chunk != v0->chunk || v->len < delay + v->chunk) {
       snprintf(g_err, sizeof g_err, "progressive_begin: decoder %d is NULL, on another device, has another chunk size or a short ring", j);
       return nullptr;
     }
@@ -1699,7 +1626,6 @@ extern "C" long v224hip_get_counter(void *p, const char *key) {
   if (!strcmp(key, "steps")) return (long)v->nsteps;
   if (strcmp(key, "chainback_redone")) return -1;
   HIPCHK(hipSetDevice(v->dev));
-  if (v->st2 != v->st) HIPCHK(hipStreamSynchronize(v->st2));
   HIPCHK(hipMemcpyAsync(&c, v->dmisc + 96, sizeof c, hipMemcpyDeviceToHost, v->st));
   HIPCHK(hipMemsetAsync(v->dmisc + 96, 0, sizeof c, v->st));
   HIPCHK(hipStreamSynchronize(v->st));
@@ -1713,7 +1639,6 @@ extern "C" int v224hip_sync(void *p) {
   if (!v) return -1;
   if (hipSetDevice(v->dev) != hipSuccess) return -1;
   if (hipStreamSynchronize(v->st) != hipSuccess) return -1;
-  if (v->st2 != v->st && hipStreamSynchronize(v->st2) != hipSuccess) return -1;
   return 0;
 }
 

@@ -35,24 +35,11 @@ __host__ __device__ constexpr unsigned lds8_qmask(int t) {
 // One packed butterfly (two x at once), the port's own candidates  old + bm  /  old + 510 - bm
 // (port.c:171-176) in packed u16.  Measured on gfx950 (scratch/valu_rate.hip): VOP3P packed ops and
 // three-operand VOP3 ops (v_bfi, v_and_or, v_lshl_or, v_perm ...) issue at 4 cycles per wave64, plain VOP2
-// (v_add_u32, v_and, v_lshrrev ...) at 2.  A variant doing the four candidate sums as carry-free 32-bit
-// adds (LDS8_PK = 0) has fewer issue cycles on paper but runs 4 % slower end to end; the packed form
-// (LDS8_PK = 1, default) is kept.  (A - B) has bit 15 / 31 = (A < B) = NOT(port decision): rows hold the
-// complement (ties: A == B gives 0 = decision 1, as ">= 0" does in port.c:178).
-// Decisions are gathered into one dword per stage: insert k of the stage (k = 2*butterfly + which
-// output) sits at bit k (low half = even x) and 16 + k (odd x).
-#ifndef LDS8_PK
-#define LDS8_PK 1
-#endif
-#ifndef LDS8_ALIAS
-#define LDS8_ALIAS 0     // 1: the output image overlays the input image (32 KiB LDS per workgroup, one more barrier)
-#endif
-#ifndef LDS8_STAGGER
+// (v_add_u32, v_and, v_lshrrev ...) at 2.  (A - B) has bit 15 / 31 = (A < B) = NOT(port decision): rows hold
+// the complement (ties: A == B gives 0 = decision 1, as ">= 0" does in port.c:178).
+// Decisions are gathered into one dword per stage, each stage into its own row: insert k of the stage
+// (k = 2*butterfly + which output) sits at bit k (low half = even x) and 16 + k (odd x).
 #define LDS8_STAGGER 2     // measured: 15.31 -> 14.83 us per launch (1: 15.29, 3: 15.04, 4: 14.95, 6: 16.24)
-#endif
-#ifndef LDS8_DROW
-#define LDS8_DROW 0     // measured: one dword store per stage into its own row beats a 4-row interleave
-#endif
 template <int T, int BF>
 __device__ __forceinline__ void lds8_bfly(v2u16 (&r)[16], unsigned &acc, const unsigned C0, const unsigned N0,
                                           const unsigned C1, const unsigned N1) {
@@ -67,26 +54,14 @@ __device__ __forceinline__ void lds8_bfly(v2u16 (&r)[16], unsigned &acc, const u
   const unsigned bc = i0 ? C1 : C0, bn = i0 ? N1 : N0;          // bm and 510 - bm, per half
   const unsigned cc = sgn ? bn : bc, cn = sgn ? bc : bn;        // register parity swaps the roles
   const unsigned oi = as_u32(r[rq]), oj = as_u32(r[rj]);
-#if LDS8_PK >= 1
   const v2u16 Av = as_v2(oi) + as_v2(cc), Bv = as_v2(oj) + as_v2(cn), Cv = as_v2(oi) + as_v2(cn), Dv = as_v2(oj) + as_v2(cc);
   const unsigned A = as_u32(Av), B = as_u32(Bv), C = as_u32(Cv), D = as_u32(Dv);
   const unsigned d0 = as_u32(Av - Bv), d1 = as_u32(Cv - Dv);   // bit 15 / 31 = (A < B) = NOT decision
-#else
-  const unsigned A = oi + cc, B = oj + cn;                      // into new slot rq (2i)
-  const unsigned C = oi + cn, D = oj + cc;                      // into new slot rj (2i+1)
-  const unsigned d0 = (A + 0x80008000u) - B;                    // bit 15 / 31 = (A >= B) per half
-  const unsigned d1 = (C + 0x80008000u) - D;
-#endif
   r[rq] = __builtin_elementwise_min(as_v2(A), as_v2(B));
   r[rj] = __builtin_elementwise_min(as_v2(C), as_v2(D));
-#if LDS8_PK == 2
-  acc |= as_u32((Av - Bv) >> (unsigned short)15) << (2 * BF);       // inverted polarity (bench only)
-  acc |= as_u32((Cv - Dv) >> (unsigned short)15) << (2 * BF + 1);
-#else
   // insert k of the stage lands at bit k / 16 + k: independent shifts, no serial chain
   acc |= (d0 & 0x80008000u) >> (15 - 2 * BF);
   acc |= (d1 & 0x80008000u) >> (14 - 2 * BF);
-#endif
 }
 
 template <int T, int... BF>
@@ -140,12 +115,9 @@ __device__ __forceinline__ unsigned block_min512_in(const V224Dev *ds, unsigned 
   return r;
 }
 
-// ABL (bench builds only) is a bit mask of things to leave out: 1 trellis arithmetic, 2 global loads,
-// 4 decision stores, 8 metric stores, 16 minimum tracking
 // ---- one tile, from the LDS input image to the global stores ------------------------------------
 // `in` holds the tile as [q][x]; on return the tile's new metrics and decisions have been issued to
 // global memory (asynchronously) and `in` may be refilled.  Returns the packed minimum of the outputs.
-template <int ABL>
 __device__ __forceinline__ v2u16 lds8_tile(unsigned char *in, unsigned char *outb, const unsigned ti, const v2u16 adj2,
                                            uint16_t *__restrict__ newm, uint32_t *__restrict__ rows, int row0,
                                            const uint8_t *__restrict__ syms) {
@@ -160,15 +132,11 @@ __device__ __forceinline__ v2u16 lds8_tile(unsigned char *in, unsigned char *out
   for (int a = 0; a < 16; a++) r[a] = as_v2(*reinterpret_cast<const unsigned *>(in + (((a << 4) | qt) * 128 + xp * 4))) - adj2;
   {
     uint4 dv;
-    if constexpr (ABL & 1) dv = make_uint4(as_u32(r[0]), as_u32(r[1]), as_u32(r[2]), as_u32(r[3]));
-    else {
-      dv.x = lds8_stage<0>(r, qt, xe, syms);
-      dv.y = lds8_stage<1>(r, qt, xe, syms);
-      dv.z = lds8_stage<2>(r, qt, xe, syms);
-      dv.w = lds8_stage<3>(r, qt, xe, syms);
-    }
-    if constexpr (ABL & 4) { if ((dv.x ^ dv.y ^ dv.z ^ dv.w) == 0x12345u) rb[0] = dv.x; }
-    else { rb[0] = dv.x; rb[V224_ROWWORDS] = dv.y; rb[2 * V224_ROWWORDS] = dv.z; rb[3 * V224_ROWWORDS] = dv.w; }
+    dv.x = lds8_stage<0>(r, qt, xe, syms);
+    dv.y = lds8_stage<1>(r, qt, xe, syms);
+    dv.z = lds8_stage<2>(r, qt, xe, syms);
+    dv.w = lds8_stage<3>(r, qt, xe, syms);
+    rb[0] = dv.x; rb[V224_ROWWORDS] = dv.y; rb[2 * V224_ROWWORDS] = dv.z; rb[3 * V224_ROWWORDS] = dv.w;
   }
 #pragma unroll
   for (int a = 0; a < 16; a++) *reinterpret_cast<unsigned *>(in + (((a << 4) | qt) * 128 + xp * 4)) = as_u32(r[a]);
@@ -177,20 +145,13 @@ __device__ __forceinline__ v2u16 lds8_tile(unsigned char *in, unsigned char *out
   // level 2: slots (qt << 4) | b
 #pragma unroll
   for (int b = 0; b < 16; b++) r[b] = as_v2(*reinterpret_cast<const unsigned *>(in + (((qt << 4) | b) * 128 + xp * 4)));
-#if LDS8_ALIAS
-  __syncthreads();            // everyone has pulled its level-2 slots: the region may now take the output image
-#endif
   {
     uint4 dv;
-    if constexpr (ABL & 1) dv = make_uint4(as_u32(r[0]), as_u32(r[1]), as_u32(r[2]), as_u32(r[3]));
-    else {
-      dv.x = lds8_stage<4>(r, qt << 4, xe, syms);
-      dv.y = lds8_stage<5>(r, qt << 4, xe, syms);
-      dv.z = lds8_stage<6>(r, qt << 4, xe, syms);
-      dv.w = lds8_stage<7>(r, qt << 4, xe, syms);
-    }
-    if constexpr (ABL & 4) { if ((dv.x ^ dv.y ^ dv.z ^ dv.w) == 0x12345u) rb[0] = dv.x; }
-    else { rb[4 * V224_ROWWORDS] = dv.x; rb[5 * V224_ROWWORDS] = dv.y; rb[6 * V224_ROWWORDS] = dv.z; rb[7 * V224_ROWWORDS] = dv.w; }
+    dv.x = lds8_stage<4>(r, qt << 4, xe, syms);
+    dv.y = lds8_stage<5>(r, qt << 4, xe, syms);
+    dv.z = lds8_stage<6>(r, qt << 4, xe, syms);
+    dv.w = lds8_stage<7>(r, qt << 4, xe, syms);
+    rb[4 * V224_ROWWORDS] = dv.x; rb[5 * V224_ROWWORDS] = dv.y; rb[6 * V224_ROWWORDS] = dv.z; rb[7 * V224_ROWWORDS] = dv.w;
   }
 
   // output image [x][q]: rows of 512 B = 32 chunks of 16 B, chunk index XOR (xp & 7)
@@ -229,8 +190,7 @@ __device__ __forceinline__ v2u16 lds8_tile(unsigned char *in, unsigned char *out
     for (int i = 0; i < 4; i++) {
       const unsigned g = i * 512 + th, xl = g >> 5, c = g & 31;
       const uint4 o = *reinterpret_cast<const uint4 *>(outb + xl * 512 + ((c ^ ((xl >> 1) & 7)) * 16));
-      if constexpr (ABL & 8) { if (o.x == 0x12345u && o.y == 77u) dst[g] = o; }
-      else dst[g] = o;
+      dst[g] = o;
     }
   }
   return mnv;
@@ -239,26 +199,15 @@ __device__ __forceinline__ v2u16 lds8_tile(unsigned char *in, unsigned char *out
 // TIN: subtract (minimum of the input - BASE) while loading; TOUT: publish the minimum of the output.
 // The port's metrics never decrease, so a launch may skip one of the two: the host alternates
 // (TIN,!TOUT) / (!TIN,TOUT) inside a run of launches, the window tolerates two launches of growth.
-// ABL (bench builds only) is a bit mask of things to leave out: 1 trellis arithmetic, 2 global loads,
-// 4 decision stores, 8 metric stores, 16 minimum tracking.
-// TILES = tiles per workgroup (grid = 512 / TILES): with 2, the second tile's loads are in flight
-// while the first is computed and the first tile's stores drain while the second is computed.
-template <int ABL = 0, bool TIN = true, bool TOUT = true, int TILES = 1>
+template <bool TIN, bool TOUT>
 __global__ __launch_bounds__(512) void k_acs_lds8(const uint16_t *__restrict__ oldm, uint16_t *__restrict__ newm,
                                                   uint32_t *__restrict__ rows, int row0,
                                                   const uint8_t *__restrict__ syms, V224Dev *ds,
                                                   unsigned pass, uint32_t *rowmeta) {
-#if LDS8_ALIAS
-  __shared__ __attribute__((aligned(16))) unsigned char lds[32768 + 64];
-  unsigned *s8 = reinterpret_cast<unsigned *>(lds + 32768);
-  unsigned char *in = lds, *outb = lds;
-#else
   __shared__ __attribute__((aligned(16))) unsigned char lds[65536 + 64];
   unsigned *s8 = reinterpret_cast<unsigned *>(lds + 65536);       // 8 + 8 words of reduction scratch
   unsigned char *in = lds, *outb = lds + 32768;
-#endif
   const unsigned th = threadIdx.x;
-#if LDS8_STAGGER
   // phase offset between the two workgroups that share a CU (all 512 are resident at once and would
   // otherwise load, compute and store in lockstep): the second half of the grid starts late, so its
   // memory phases fall under the first half's arithmetic and vice versa
@@ -266,44 +215,31 @@ __global__ __launch_bounds__(512) void k_acs_lds8(const uint16_t *__restrict__ o
 #pragma unroll 1
     for (int i = 0; i < LDS8_STAGGER; i++) __builtin_amdgcn_s_sleep(32);      // 32 * 64 cycles each
   }
-#endif
 
-  // ---- loads: chunk g = i*512 + th (16 B) = row g>>3, 8 states at column (g&7)*8; all tiles up front
-  uint4 v[TILES][4];
+  // ---- loads: chunk g = i*512 + th (16 B) = row g>>3, 8 states at column (g&7)*8
+  const unsigned ti = blockIdx.x;
+  uint4 v[4];
 #pragma unroll
-  for (int t = 0; t < TILES; t++) {
-    const unsigned ti = blockIdx.x * TILES + t;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const unsigned g = i * 512 + th, q = g >> 3, c = g & 7;
-      if constexpr (ABL & 2) v[t][i] = make_uint4(g * 2654435761u & 0x3fff3fffu, g & 0xfff, th, ti);
-      else v[t][i] = *reinterpret_cast<const uint4 *>(oldm + ((size_t)q << 15) + ti * 64 + c * 8);
-    }
+  for (int i = 0; i < 4; i++) {
+    const unsigned g = i * 512 + th, q = g >> 3, c = g & 7;
+    v[i] = *reinterpret_cast<const uint4 *>(oldm + ((size_t)q << 15) + ti * 64 + c * 8);
   }
 #pragma unroll
-  for (int i = 0; i < 4; i++) *reinterpret_cast<uint4 *>(in + (i * 512 + th) * 16) = v[0][i];
+  for (int i = 0; i < 4; i++) *reinterpret_cast<uint4 *>(in + (i * 512 + th) * 16) = v[i];
   unsigned adj;
-  if constexpr ((ABL & 16) || !TIN) { adj = 0; __syncthreads(); }
+  if constexpr (!TIN) { adj = 0; __syncthreads(); }
   else adj = block_min512_in(ds, pass, s8) - V224_BASE;            // contains the barrier after the LDS fill
   const v2u16 adj2 = as_v2((adj & 0xffffu) * 0x10001u);
 
-  v2u16 mnv = lds8_tile<ABL>(in, outb, blockIdx.x * TILES, adj2, newm, rows, row0, syms);
-#pragma unroll
-  for (int t = 1; t < TILES; t++) {
-    // level 2 of the previous tile finished reading `in` before its last barrier
-#pragma unroll
-    for (int i = 0; i < 4; i++) *reinterpret_cast<uint4 *>(in + (i * 512 + th) * 16) = v[t][i];
-    __syncthreads();                                    // also: everyone is done copying the old output image
-    mnv = __builtin_elementwise_min(mnv, lds8_tile<ABL>(in, outb, blockIdx.x * TILES + t, adj2, newm, rows, row0, syms));
-  }
+  const v2u16 mnv = lds8_tile(in, outb, ti, adj2, newm, rows, row0, syms);
 
   // ---- minimum of what this workgroup wrote ----------------------------------------------------
-  if constexpr (!(ABL & 16) && !TOUT) {
+  if constexpr (!TOUT) {
     if (th == 0 && blockIdx.x == 0) {
       ds->off += (long long)(int)adj;
       for (int t = 0; t < 8; t++) rowmeta[row0 + t] = LDS8_META(t + 1);
     }
-  } else if constexpr (!(ABL & 16)) {
+  } else {
     unsigned mn = (unsigned)mnv.x < (unsigned)mnv.y ? (unsigned)mnv.x : (unsigned)mnv.y;
     mn = wave_min_u32(mn);
     if ((th & 63) == 0) s8[8 + (th >> 6)] = mn;
@@ -319,7 +255,7 @@ __global__ __launch_bounds__(512) void k_acs_lds8(const uint16_t *__restrict__ o
         for (int t = 0; t < 8; t++) rowmeta[row0 + t] = LDS8_META(t + 1);
       }
     }
-  } else if (mnv.x == 0x7777 && th == 0) ds->off = 1;
+  }
 }
 
 // decision for NEW state s of the row written by stage tau (1..8) of an LDS pass; r = that row's base
@@ -327,18 +263,12 @@ __device__ __forceinline__ unsigned lds8_get_decision(const uint32_t *__restrict
   const unsigned x = (s >> tau) & 0x7fffu;
   const unsigned qout = ((s & ((1u << tau) - 1u)) << (8 - tau)) | (s >> (15 + tau));
   const unsigned ti = x >> 6, xl = x & 63u, xp = xl >> 1, h = xl & 1u;
-  const unsigned j = (tau - 1u) & 3u, lb = 3u - j;
+  const unsigned lb = 3u - ((tau - 1u) & 3u);
   unsigned th, slot;
   if (tau <= 4) { th = ((qout & 15u) << 5) | xp; slot = qout >> 4; }
   else          { th = ((qout >> 4) << 5) | xp;  slot = qout & 15u; }
   // insert order inside a stage: butterfly BF = slot with bit lb squeezed out, low slot first
   const unsigned bf = ((slot >> (lb + 1)) << lb) | (slot & ((1u << lb) - 1u));
   const unsigned bit = 16u * h + 2u * bf + ((slot >> lb) & 1u);
-  const unsigned inv = LDS8_PK >= 1 ? 1u : 0u;                    // packed path stores NOT(decision)
-#if LDS8_DROW == 0
-  return ((r[ti * 512u + th] >> bit) & 1u) ^ inv;
-#else
-  const uint32_t *grp = r - (size_t)j * V224_ROWWORDS;            // first row of the 4-row group
-  return ((grp[(ti * 512u + th) * 4u + j] >> bit) & 1u) ^ inv;
-#endif
+  return ((r[ti * 512u + th] >> bit) & 1u) ^ 1u;                  // rows hold NOT(decision)
 }

@@ -10,8 +10,7 @@
 //      phys(s) = (s >> 15) << 15 | (s & 0xff) << 7 | (s >> 8) & 0x7f
 // A tile's OUTPUT (new states s' = x << 15 | q) is then one contiguous 64 KiB block, row q & 0xff, column q >> 8,
 // and its INPUT 256 runs of 256 B, one from every tile of the previous pass.  (With the natural layout the reads
-// would be 2-byte gathers: old[(q << 8) + x]; the reverse assignment -- contiguous reads, strided writes -- is
-// L15_WMAJOR = 0.)
+// would be 2-byte gathers: old[(q << 8) + x].)
 //
 // 1024 threads x 16 packed VGPRs (two slots per VGPR) = 32 768 slots.  Four register levels with the tile in LDS
 // between them (each exchange: 16 ds_write_b32 in place, barrier, 16 ds_read_b32 / 4 ds_read_b128):
@@ -26,71 +25,12 @@
 // So the LDS holds only the in-place tile (70 KiB: two workgroups, of two decoders, fit a CU), there are three
 // barriers, and PMC reports no bank conflict: the image is padded by 4 dwords per 64 and 8 per 1024 (dword d sits at
 // d + (d >> 6) * 4 + (d >> 10) * 8), which keeps every per-register offset an immediate.
-// (L15_L0DIRECT = 0 / L15_DIRECTOUT = 0 are the earlier forms: tile copied into LDS first / output image in LDS.)
 //
 // Decisions: one dword per thread and stage, word index x * 1024 + thread, bit 8*(2*which output + half) +
 // butterfly; rows hold NOT(decision) as in the other packed engines.  A pass may wrap the ring.
 #pragma once
 
-#ifndef L15_DECPERM
-#define L15_DECPERM 1
-#endif
-#ifndef L15_DECSIGN
-#define L15_DECSIGN 1     // (with L15_DECPERM) 1: v_perm's sign-replicating selectors give the four decisions as 0x00 / 0xff bytes,
-#endif                    //    one v_bfi under a per-butterfly mask puts them in place: 2 instructions per butterfly instead of 3
-                          //    (15 instead of 22 per stage, 1 437 -> 1 332 per wave); 0: byte gather, shift, merge
-#ifndef L15_WMAJOR
-#define L15_WMAJOR 1      // 1: a tile's OUTPUT is the contiguous 64 KiB block and its input 256 runs of 256 B; 0: the reverse
-#endif
-#ifndef L15_DSTORE
-#define L15_DSTORE 1      // decision-store cache policy: 0 plain, 1 nontemporal, 2 sc0 sc1 (write-through), 3 nt sc0 sc1
-#endif
-#ifndef L15_L0DIRECT
-#define L15_L0DIRECT 1    // 1: level 0 takes its 16 dwords straight from HBM (each wave instruction = one 256-byte run);
-#endif                    //    0: the tile is first copied into LDS (4 x 16 B per thread) and read back from there
-#ifndef L15_MINFIRST
-#define L15_MINFIRST 1    // 1: the previous launch's minima are loaded before the metrics, their reduction runs under the metric loads
-#endif
-#ifndef L15_ROTTAB
-#define L15_ROTTAB 1      // 1: per-thread stage parities from l15_rot_tab (4 loads per thread); 0: counted (and + bcnt + shift per stage)
-#endif
-#ifndef L15_DIRECTOUT
-#define L15_DIRECTOUT 1   // 1: level 3 maps lanes to output columns, so a wave holds complete 256-byte output rows and stores
-#endif                    //    them straight from registers; 0: output image in LDS, one more barrier, lane-contiguous copy-out
-#ifndef L15_LATEADJ
-#define L15_LATEADJ 1     // 1: the input normalisation (subtract the previous launch's minimum - BASE) is folded into stage 5's
-#endif                    //    constants instead of stage 1's: the minima's load, wave reduction and LDS hand-over then have
-                          //    the whole of level 0 to finish and share the barrier of the first tile exchange; 0: stage 1
-#define L15_ADJ_STAGE (L15_LATEADJ ? 4 : 0)
-#ifndef L15_EARLYSTART
-#define L15_EARLYSTART 0  // 1: the sixteen metric loads are issued in the order stage 1 pairs them (0, 8, 1, 9, ...) and every
-#endif                    //    butterfly of stage 1 waits only for its own two (vmcnt 14, 12, ... 0); 0: one wait for all sixteen.
-                          //    Measured: a lone launch 16.70 -> 16.46 us with it, but TWO decoders side by side fall from 21.6 to
-                          //    26 us per launch pair (their launch chains run in lock-step, DESIGN.md section 8): off
-#ifndef L15_PRIO
-#define L15_PRIO 1        // 1: the four waves of a SIMD run level 3 (no barrier behind it) at staggered priorities, so that the
-#endif                    //    first wave's metric stores leave while the others still compute; 2: staggered from the start.
-                          //    What it does to ONE launch is nothing (16.15 -> 16.21 us); what it does to a PAIR of launch chains
-                          //    depends on the rest of the kernel: with the three-instruction decision packing it put every pair
-                          //    in lock-step (2.24 against 2.66 Msymbols/s, profiles/r03c_*), with the two-instruction packing it
-                          //    is the build that pairs well (2.73-2.79 against 2.39-2.41 without it and 2.60-2.66 for the old
-                          //    kernel on the same boxes, profiles/r03av_*, r03aw_*).  DESIGN.md section 8, "lock-step".
-#ifndef L15_MSTORE
-#define L15_MSTORE 0      // metric-store cache policy (level 3, rows straight from registers): 0 plain, 1 nt, 2 sc0 sc1, 3 nt sc0 sc1
-#endif
-__device__ __forceinline__ void l15_mstore(unsigned char *p, uint2 w) {
-#if L15_MSTORE == 0
-  *reinterpret_cast<uint2 *>(p) = w;
-#elif L15_MSTORE == 1
-  asm volatile("global_store_dwordx2 %0, %1, off nt" :: "v"(p), "v"(w) : "memory");
-#elif L15_MSTORE == 2
-  asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1" :: "v"(p), "v"(w) : "memory");
-#else
-  asm volatile("global_store_dwordx2 %0, %1, off nt sc0 sc1" :: "v"(p), "v"(w) : "memory");
-#endif
-}
 // waves w, w + 4, w + 8, w + 12 of a workgroup share a SIMD: priorities 3, 2, 1, 0 (s_setprio takes an immediate)
-// (reversed priorities, two levels instead of four, staggering from level 2 on: the same pair rates, profiles/r03az_*)
 __device__ __forceinline__ void l15_stagger_prio(unsigned th) {
   const unsigned rank = (unsigned)__builtin_amdgcn_readfirstlane((int)(th >> 8));
   if (rank == 0) __builtin_amdgcn_s_setprio(3);
@@ -99,15 +39,15 @@ __device__ __forceinline__ void l15_stagger_prio(unsigned th) {
   else __builtin_amdgcn_s_setprio(0);
 }
 #define LDS15_META(tau) ((1u << 17) | (15u << 8) | (unsigned)(tau))
-// input image: dword d sits at d + (d >> 6) * 4 [+ (d >> 10) * 8 with L15_DIRECTOUT: the level-3 lanes then differ in
-// d bits 10..13 and would otherwise fall on the same banks]
-#define L15_PADA       (L15_DIRECTOUT ? 1096u : 1088u)      // dwords per 1024-dword slab
-#define L15_IN_BYTES   (L15_DIRECTOUT ? 70144u : 69632u)   // (16384 + 1024 [+ 128]) dwords
-#define L15_OUT_BYTES  66048u                 // 256 rows x 256 B + 31 x 16 B of padding, rounded up
-#ifndef L15_ALIAS
-#define L15_ALIAS 1       // 1: the output image overlays the input image (one more barrier): 68 KiB of LDS per workgroup,
-#endif                    //    so two workgroups -- of two decoders on two streams -- fit one CU and overlap their phases
-#define L15_LDS_BYTES  ((L15_ALIAS || L15_DIRECTOUT) ? L15_IN_BYTES + 128u : L15_IN_BYTES + L15_OUT_BYTES + 128u)
+// input image: dword d sits at d + (d >> 6) * 4 + (d >> 10) * 8 (the level-3 lanes differ in d bits 10..13 and would
+// otherwise fall on the same banks)
+#define L15_PADA       1096u                  // dwords per 1024-dword slab
+#define L15_IN_BYTES   70144u                 // (16384 + 1024 + 128) dwords
+#define L15_LDS_BYTES  70272u                 // the image + 128 bytes of reduction scratch
+// The input normalisation (subtract the previous launch's minimum - BASE) is folded into stage 5's constants, not
+// stage 1's: the minima's load, wave reduction and LDS hand-over then have the whole of level 0 to finish and share
+// the barrier of the first tile exchange.
+#define L15_ADJ_STAGE  4
 
 __host__ __device__ constexpr int l15_qpos(int j, int t) { return j >= 15 - t ? j - (15 - t) : j + t + 8; }
 __host__ __device__ constexpr unsigned l15_qmask(int t) {
@@ -141,38 +81,18 @@ __device__ __forceinline__ void l15_bfly(v2u16 (&r)[16], unsigned &acc, const v2
   const v2u16 K = i0 ? K1 : K0;
   const v2u16 cc = __builtin_shufflevector(K, K, (int)sgn, (int)(sgn ^ kh));
   const v2u16 cn = __builtin_shufflevector(K, K, (int)(sgn ^ 1u), (int)(sgn ^ kh ^ 1u));
-#if L15_EARLYSTART && L15_L0DIRECT && L15_WMAJOR
-  if constexpr (T == 0)      // level 0 takes its operands straight from HBM: this butterfly's pair is loads 2 BF and 2 BF + 1 of sixteen
-    asm volatile("s_waitcnt vmcnt(%2)" : "+v"(r[rq]), "+v"(r[rj]) : "n"(14 - 2 * BF) : "memory");
-#endif
   const v2u16 oi = r[rq], oj = r[rj];
   const v2u16 Av = oi + cc, Bv = oj + cn, Cv = oi + cn, Dv = oj + cc;
   const unsigned d0 = as_u32(Av - Bv), d1 = as_u32(Cv - Dv);       // bit 15 / 31 = (A < B) = NOT decision
   r[rq] = __builtin_elementwise_min(Av, Bv);
   r[rj] = __builtin_elementwise_min(Cv, Dv);
-#if L15_DECPERM
-  // the four sign bits sit at bit 7 of bytes 1 and 3 of d0, d1: gather those bytes with one v_perm, then shift
-  // the accumulator and merge bit 7 of every byte under a mask (v_bfi): 3 instructions per butterfly instead
-  // of 5.  Insert k of the stage ends at bit k of byte 2*which + half; what the first insert leaves in bits
-  // 0..6 is shifted out (into a bit 7 that the next merge overwrites).
-#if L15_DECSIGN
-  // selectors 8 .. 11 of v_perm_b32 replicate the sign bit of bytes 1, 3, 5, 7 of {d1, d0} over a whole byte: P holds the four
-  // decisions as 0x00 / 0xff.  Butterfly 0 fills all eight bits of every byte with its decision; butterfly k overwrites bit k.
+  // The four sign bits sit at bit 7 of bytes 1 and 3 of d0, d1.  Selectors 8 .. 11 of v_perm_b32 replicate the sign bit
+  // of bytes 1, 3, 5, 7 of {d1, d0} over a whole byte: P holds the four decisions as 0x00 / 0xff, byte 2*which + half.
+  // Butterfly 0 fills all eight bits of every byte with its decision; butterfly k overwrites bit k under a mask
+  // (v_bfi): 2 instructions per butterfly.
   const unsigned P = __builtin_amdgcn_perm(d1, d0, 0x0b0a0908u);
   if constexpr (BF == 0) acc = P;
   else asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(acc) : "s"(0x01010101u << BF), "v"(P), "v"(acc));
-#else
-  const unsigned P = __builtin_amdgcn_perm(d1, d0, 0x07050301u);
-  if constexpr (BF == 0) acc = P;
-  else {
-    const unsigned sh = acc >> 1;
-    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(acc) : "s"(0x80808080u), "v"(P), "v"(sh));
-  }
-#endif
-#else
-  acc |= (d0 & 0x80008000u) >> (15 - 2 * BF);
-  acc |= (d1 & 0x80008000u) >> (14 - 2 * BF);
-#endif
 }
 
 template <int T, int... BF>
@@ -216,11 +136,7 @@ __host__ __device__ constexpr unsigned l15_qthr(int level, unsigned th) {
   return level == 0 ? th << 1
        : level == 1 ? ((th >> 6) << 11) | ((th & 63u) << 1)
        : level == 2 ? ((th >> 2) << 7) | ((th & 3u) << 1)
-#if L15_DIRECTOUT
        : ((((th >> 2) & 15u) << 11) | (((th >> 1) & 1u) << 10) | ((th & 1u) << 7) | ((th >> 6) << 3));
-#else
-       : (((th >> 6) << 11) | (((th >> 5) & 1u) << 7) | (((th >> 4) & 1u) << 10) | ((th & 15u) << 3));
-#endif
 }
 static void l15_build_rot_tab(unsigned *tab) {
   for (int level = 0; level < 4; level++)
@@ -246,12 +162,8 @@ __device__ __forceinline__ unsigned l15_stage(v2u16 (&r)[16], const unsigned qth
   constexpr unsigned xmask = (V224_P1H >> T) & 0xffu;
   // parity of the thread's part of the state number: looked up, not counted -- rotw = the thread's word of l15_rot_tab for
   // this level, field k (5 bits) = 16 * parity(qthr & qmask(4 level + k)); v_alignbit uses bits 4..0 of its shift: 0 or 16
-#if L15_ROTTAB
   const unsigned rot = (T & 3) ? rotw >> (5 * (T & 3)) : rotw;
-#else
-  const unsigned rot = (unsigned)__popc(qthr & l15_qmask(T)) << 4;
-#endif
-  // scalar pairs: half 0 = bm for even parity, half 1 = 510 - bm; stage 1 also carries the input normalisation; the
+  // scalar pairs: half 0 = bm for even parity, half 1 = 510 - bm; stage 5 also carries the input normalisation; the
   // tile's own parity (x is uniform) swaps the halves on the scalar side
   const unsigned a16 = (T == L15_ADJ_STAGE) ? adj : 0u;
   const unsigned px = (unsigned)__popc(x & xmask) & 1u;
@@ -275,72 +187,28 @@ __device__ __forceinline__ unsigned l15_stage(v2u16 (&r)[16], const unsigned qth
   return acc;
 }
 
-__device__ __forceinline__ void l15_dstore(uint32_t *p, unsigned v) {
-#if L15_DSTORE == 0
-  *p = v;
-#elif L15_DSTORE == 1
-  __builtin_nontemporal_store(v, p);
-#elif L15_DSTORE == 2
-  asm volatile("global_store_dword %0, %1, off sc0 sc1" :: "v"(p), "v"(v) : "memory");
-#else
-  asm volatile("global_store_dword %0, %1, off nt sc0 sc1" :: "v"(p), "v"(v) : "memory");
-#endif
-}
-// minimum of the previous launch's per-workgroup minima, reduced by the 16 waves (contains a barrier)
-__device__ __forceinline__ unsigned block_min1024_in(const V224Dev *ds, unsigned pass, unsigned *s16) {
-  const unsigned *a = ds->blkmin[pass & 1];
-  const unsigned n = ds->nmin[pass & 1];
-  unsigned m = 0xffffffffu;
-  for (unsigned i = threadIdx.x; i < n; i += 1024) { unsigned v = a[i]; m = v < m ? v : m; }
-  m = wave_min_u32(m);
-  if ((threadIdx.x & 63) == 0) s16[threadIdx.x >> 6] = m;
-  __syncthreads();
-  unsigned r = s16[0];
-#pragma unroll
-  for (int w = 1; w < 16; w++) r = s16[w] < r ? s16[w] : r;
-  return r;
-}
+// decision rows are written once and read back only by the traceback: nontemporal
+__device__ __forceinline__ void l15_dstore(uint32_t *p, unsigned v) { __builtin_nontemporal_store(v, p); }
 
-// ABL (bench builds only): 1 no trellis arithmetic, 4 no decision stores, 8 no metric stores, 16 no minimum tracking
-template <int ABL = 0, bool TIN = true, bool TOUT = true>
+// NOARITH: the placement probe's build (place_metrics): the same loads, LDS traffic and stores, no trellis arithmetic
+template <bool NOARITH, bool TIN, bool TOUT>
 __global__ __launch_bounds__(1024) void k_acs_lds15(const uint16_t *__restrict__ oldm, uint16_t *__restrict__ newm,
                                                     uint32_t *__restrict__ rows, int row0, int len,
                                                     const uint8_t *__restrict__ syms, V224Dev *ds,
                                                     unsigned pass, uint32_t *rowmeta) {
   extern __shared__ __attribute__((aligned(16))) unsigned char l15_lds[];
-  unsigned char *in = l15_lds, *outb = L15_ALIAS ? l15_lds : l15_lds + L15_IN_BYTES;
-  (void)outb;
+  unsigned char *in = l15_lds;
   unsigned *s16 = reinterpret_cast<unsigned *>(l15_lds + L15_LDS_BYTES - 128u);           // 16 + 16 words
   const unsigned th = threadIdx.x, x = blockIdx.x;
-#if L15_PRIO == 2
-  l15_stagger_prio(th);
-#endif
   const L15Syms sy = l15_load_syms(syms);          // before any store of this kernel: scalar loads
-#if L15_ROTTAB && L15_EARLYSTART && L15_L0DIRECT && L15_WMAJOR
-  // asm like the metric loads: the compiler would otherwise wait for "its" four loads with a vmcnt that also counts the
-  // seventeen asm loads issued behind them, i.e. for nearly everything
-  unsigned rw0, rw1, rw2, rw3;
-  {
-    const unsigned *tab = l15_rot_tab;
-    const unsigned toff = th << 2;
-    asm volatile("global_load_dword %0, %1, %2" : "=v"(rw0) : "v"(toff), "s"(tab) : "memory");
-    asm volatile("global_load_dword %0, %1, %2" : "=v"(rw1) : "v"(toff), "s"(tab + 1024) : "memory");
-    asm volatile("global_load_dword %0, %1, %2" : "=v"(rw2) : "v"(toff), "s"(tab + 2048) : "memory");
-    asm volatile("global_load_dword %0, %1, %2" : "=v"(rw3) : "v"(toff), "s"(tab + 3072) : "memory");
-  }
-#elif L15_ROTTAB
   const unsigned rw0 = l15_rot_tab[th], rw1 = l15_rot_tab[1024 + th], rw2 = l15_rot_tab[2048 + th], rw3 = l15_rot_tab[3072 + th];
-#else
-  const unsigned rw0 = 0, rw1 = 0, rw2 = 0, rw3 = 0;
-#endif
 
   v2u16 r[16], mnv;
-#if L15_L0DIRECT && L15_WMAJOR && L15_MINFIRST
   // The previous launch's per-workgroup minima go FIRST into the memory pipeline (vector loads return in order): their
   // reduction and its barrier then run while the sixteen metric loads behind them are still in flight, instead of after
   // them.  asm, because the compiler would wait for this load with vmcnt(0) -- i.e. for the metric loads as well.
   unsigned mpre = 0xffffffffu, nmin_v = 0u;
-  if constexpr (TIN && !(ABL & 16)) {
+  if constexpr (TIN) {
     // entry th of the writer's minima (1 .. 512 of them, one per workgroup; the array holds 4 096 words, so the load is in
     // bounds whatever their number) AND their number, both at once: fetching the number first and then entry
     // min(th, n - 1) put a whole memory round trip in front of the metric loads.  Entries beyond the number are dropped below.
@@ -349,90 +217,36 @@ __global__ __launch_bounds__(1024) void k_acs_lds15(const uint16_t *__restrict__
     asm volatile("global_load_dword %0, %1, %2" : "=v"(mpre) : "v"(th << 2), "s"(a) : "memory");
     asm volatile("global_load_dword %0, %1, %2" : "=v"(nmin_v) : "v"(0u), "s"(np) : "memory");
   }
-#endif
-#if L15_L0DIRECT && L15_WMAJOR
   // ---- level 0 operands straight from HBM: register a of thread th is dword (th & 63) of run (a << 4 | th >> 6),
   //      the 256 bytes that tile (a << 4 | th >> 6) of the previous pass wrote for this x
   {
     // uniform base (tile x, run a) in SGPRs + ONE 32-bit per-thread byte offset: global_load_dword vdst, voff, s[base].
     // Written as asm because the compiler folds base and offset into sixteen 64-bit VGPR addresses otherwise (30 VALU
-    // instructions and 30 VGPRs).  The loads are waited for by l15_wait_loads() below (the compiler does not count them).
+    // instructions and 30 VGPRs).  The loads are waited for below (the compiler does not count them).  One wait for all
+    // sixteen, not one per butterfly of stage 1: see DESIGN.md section 8, "lock-step".
     const unsigned char *base = reinterpret_cast<const unsigned char *>(oldm) + ((size_t)x << 8);
     const unsigned voff = ((th >> 6) << 16) | ((th & 63u) << 2);
 #pragma unroll
-    for (int i = 0; i < 16; i++) {                                             // run + 16: 16 x 32768 u16 = 2^20 bytes
-      const int a = L15_EARLYSTART ? ((i & 1) << 3) | (i >> 1) : i;           // 0, 8, 1, 9, ...: the order stage 1 pairs them in
+    for (int a = 0; a < 16; a++) {                                             // run + 16: 16 x 32768 u16 = 2^20 bytes
       unsigned v;
       asm volatile("global_load_dword %0, %1, %2" : "=v"(v) : "v"(voff), "s"(base + ((size_t)a << 20)) : "memory");
       r[a] = as_v2(v);
     }
   }
-#else
-  // ---- fill: 16-byte chunk g -> chunk g + (g >> 4) of the padded image
-  {
-    uint4 v[4];
-#if L15_WMAJOR
-#pragma unroll
-    for (int i = 0; i < 4; i++) {                     // chunk g of the tile = run g >> 4 (written by tile g >> 4), piece g & 15
-      const unsigned g = i * 1024 + th;
-      v[i] = reinterpret_cast<const uint4 *>(oldm + (((size_t)(g >> 4) << 15) | ((size_t)x << 7)))[g & 15u];
-    }
-#else
-    const uint4 *src = reinterpret_cast<const uint4 *>(oldm + (size_t)x * 32768u);
-#pragma unroll
-    for (int i = 0; i < 4; i++) v[i] = src[i * 1024 + th];
-#endif
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const unsigned g = i * 1024 + th;
-      *reinterpret_cast<uint4 *>(in + (g + (g >> 4) + (L15_DIRECTOUT ? (g >> 8) * 2u : 0u)) * 16u) = v[i];
-    }
-  }
-#endif
-  unsigned adj;
-  if constexpr ((ABL & 16) || !TIN) {
-    adj = 0;
-#if !(L15_L0DIRECT && L15_WMAJOR)
-    __syncthreads();                                               // the fill must be complete
-#endif
-  }
-#if L15_L0DIRECT && L15_WMAJOR && L15_MINFIRST
-  else {
+  // Uniform offsets do not enter any decision (only differences do), and four more steps of growth (4 x 510) stay inside
+  // the u16 window: 4096 + 12 730 + 15 x 510 of an un-adjusted predecessor + 2 040 = 26 516 < 2^15.  So level 0 runs on
+  // the metrics as they are; the wave minima wait in LDS behind the barrier of the first tile exchange.
+  unsigned adj = 0;
+  if constexpr (TIN) {
     asm volatile("s_waitcnt vmcnt(16)" : "+v"(mpre), "+v"(nmin_v));  // the minima have landed (the 16 loads behind them may not have)
     unsigned m = wave_min_u32(th < nmin_v ? mpre : 0xffffffffu);
     if ((th & 63u) == 0) s16[th >> 6] = m;
-#if L15_LATEADJ
-    // Uniform offsets do not enter any decision (only differences do), and four more steps of growth (4 x 510) stay inside
-    // the u16 window: 4096 + 12 730 + 15 x 510 of an un-adjusted predecessor + 2 040 = 26 516 < 2^15.  So level 0 runs on
-    // the metrics as they are; the wave minima wait in LDS behind the barrier of the first tile exchange.
-    adj = 0;
-#else
-    __syncthreads();
-    unsigned q = s16[0];
-#pragma unroll
-    for (int w = 1; w < 16; w++) q = s16[w] < q ? s16[w] : q;
-    adj = q - V224_BASE;
-#endif
   }
-#else
-  else adj = block_min1024_in(ds, pass, s16) - V224_BASE;          // contains a barrier (also the one after the fill)
-#endif
-
-#if L15_L0DIRECT && L15_WMAJOR && L15_EARLYSTART
-  // the four table words (and the minima) are older than the sixteen metric loads: landed once at most sixteen are out
-  asm volatile("s_waitcnt vmcnt(16)" : "+v"(rw0), "+v"(rw1), "+v"(rw2), "+v"(rw3) :: "memory");
-  if constexpr (ABL & 1)      // bench / placement-probe builds without the arithmetic: nothing else would wait for the metrics
-    asm volatile("s_waitcnt vmcnt(0)"
-                 : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7]),
-                   "+v"(r[8]), "+v"(r[9]), "+v"(r[10]), "+v"(r[11]), "+v"(r[12]), "+v"(r[13]), "+v"(r[14]), "+v"(r[15])
-                 :: "memory");
-#elif L15_L0DIRECT && L15_WMAJOR
   // the sixteen asm loads above have landed after this (ties the registers to the wait so that no use moves above it)
   asm volatile("s_waitcnt vmcnt(0)"
                : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7]),
                  "+v"(r[8]), "+v"(r[9]), "+v"(r[10]), "+v"(r[11]), "+v"(r[12]), "+v"(r[13]), "+v"(r[14]), "+v"(r[15])
                :: "memory");
-#endif
   // decision rows of the 15 stages (the pass may wrap the ring): uniform row base + per-thread word
   const unsigned woffb = (x * 1024u + th) * 4u;            // 32-bit byte offset: uniform base + per-lane offset addressing
 #define L15_ROW(t) reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(rows + (size_t)((row0 + (t)) >= len ? row0 + (t) - len : row0 + (t)) * V224_ROWWORDS) + woffb)
@@ -440,37 +254,30 @@ __global__ __launch_bounds__(1024) void k_acs_lds15(const uint16_t *__restrict__
   {                                                                                                \
     const unsigned d0_ = l15_stage<T0>(r, QTHR, x, sy, adj, RW), d1_ = l15_stage<T0 + 1>(r, QTHR, x, sy, adj, RW); \
     const unsigned d2_ = l15_stage<T0 + 2>(r, QTHR, x, sy, adj, RW), d3_ = l15_stage<T0 + 3>(r, QTHR, x, sy, adj, RW); \
-    if constexpr (ABL & 4) { if ((d0_ ^ d1_ ^ d2_ ^ d3_) == 0x12345u) l15_dstore(L15_ROW(T0), d0_); }   \
-    else { l15_dstore(L15_ROW(T0), d0_); l15_dstore(L15_ROW(T0 + 1), d1_); l15_dstore(L15_ROW(T0 + 2), d2_); l15_dstore(L15_ROW(T0 + 3), d3_); } \
+    l15_dstore(L15_ROW(T0), d0_); l15_dstore(L15_ROW(T0 + 1), d1_); l15_dstore(L15_ROW(T0 + 2), d2_); l15_dstore(L15_ROW(T0 + 3), d3_); \
   }
 
   // ---- level 0: slots a << 11 | th << 1 | h ; dword a << 10 | th
   {
     unsigned char *p = in + (th + (th >> 6) * 4u) * 4u;
-#if !(L15_L0DIRECT && L15_WMAJOR)
-#pragma unroll
-    for (int a = 0; a < 16; a++) r[a] = as_v2(*reinterpret_cast<const unsigned *>(p + a * (L15_PADA * 4)));
-#endif
-    if constexpr (!(ABL & 1)) L15_STAGES4(0, th << 1, rw0)               // (the input normalisation happens inside stage 1)
+    if constexpr (!NOARITH) L15_STAGES4(0, th << 1, rw0)
 #pragma unroll
     for (int a = 0; a < 16; a++) *reinterpret_cast<unsigned *>(p + a * (L15_PADA * 4)) = as_u32(r[a]);
   }
   __syncthreads();
-#if L15_LATEADJ && L15_L0DIRECT && L15_WMAJOR && L15_MINFIRST
-  if constexpr (TIN && !(ABL & 16)) {                  // the previous launch's minimum, handed over in LDS before the barrier above
+  if constexpr (TIN) {                  // the previous launch's minimum, handed over in LDS before the barrier above
     unsigned q = s16[0];
 #pragma unroll
     for (int w = 1; w < 16; w++) q = s16[w] < q ? s16[w] : q;
     adj = q - V224_BASE;
   }
-#endif
   // ---- level 1: slots hi4 << 11 | a << 7 | lo6 << 1 | h ; dword hi4 << 10 | a << 6 | lo6
   {
     const unsigned hi4 = th >> 6, lo6 = th & 63u;
     unsigned char *p = in + hi4 * (L15_PADA * 4u) + lo6 * 4u;
 #pragma unroll
     for (int a = 0; a < 16; a++) r[a] = as_v2(*reinterpret_cast<const unsigned *>(p + a * 272));
-    if constexpr (!(ABL & 1)) L15_STAGES4(4, (hi4 << 11) | (lo6 << 1), rw1)
+    if constexpr (!NOARITH) L15_STAGES4(4, (hi4 << 11) | (lo6 << 1), rw1)
 #pragma unroll
     for (int a = 0; a < 16; a++) *reinterpret_cast<unsigned *>(p + a * 272) = as_u32(r[a]);
   }
@@ -478,32 +285,23 @@ __global__ __launch_bounds__(1024) void k_acs_lds15(const uint16_t *__restrict__
   // ---- level 2: slots hi8 << 7 | a << 3 | lo2 << 1 | h ; dword hi8 << 6 | a << 2 | lo2
   {
     const unsigned hi8 = th >> 2, lo2 = th & 3u;
-    unsigned char *p = in + hi8 * 272u + (L15_DIRECTOUT ? (hi8 >> 4) * 32u : 0u) + lo2 * 4u;
+    unsigned char *p = in + hi8 * 272u + (hi8 >> 4) * 32u + lo2 * 4u;
 #pragma unroll
     for (int a = 0; a < 16; a++) r[a] = as_v2(*reinterpret_cast<const unsigned *>(p + a * 16));
-    if constexpr (!(ABL & 1)) L15_STAGES4(8, (hi8 << 7) | (lo2 << 1), rw2)
+    if constexpr (!NOARITH) L15_STAGES4(8, (hi8 << 7) | (lo2 << 1), rw2)
 #pragma unroll
     for (int a = 0; a < 16; a++) *reinterpret_cast<unsigned *>(p + a * 16) = as_u32(r[a]);
   }
   __syncthreads();
-#if L15_PRIO == 1
+  // level 3 has no barrier behind it: staggered priorities let the first wave's metric stores leave while the others
+  // still compute.  That is what makes two decoders' launch chains pair well: DESIGN.md section 8, "lock-step".
   l15_stagger_prio(th);
-#endif
-#if L15_DIRECTOUT
   // ---- level 3: wave = t63 (slots 6..3), lanes = t14 (slots 14..11) | t10 | t7: for one register the 64 lanes hold
   //      two complete output rows (row = slots 7..0, 128 columns = slots 14..8); register a = b9:b2:b1:b0, packed over
   //      slot bit 8
   {
     const unsigned t63 = th >> 6, t14 = (th >> 2) & 15u, t10 = (th >> 1) & 1u, t7 = th & 1u;
     const unsigned char *p = in + (t14 * L15_PADA + t10 * 544u + t7 * 68u + t63 * 4u) * 4u;
-#else
-  // ---- level 3: thread bits t14 = th[9:6] (slots 14..11), t7 = th[5], t10 = th[4], t63 = th[3:0] (slots 6..3)
-  //      (lanes 0..31 then span all 64 banks in the ds_write_b64 of the output image);
-  //      register a = b9:b2:b1:b0, packed over slot bit 8
-  {
-    const unsigned t14 = th >> 6, t7 = (th >> 5) & 1u, t10 = (th >> 4) & 1u, t63 = th & 15u;
-    const unsigned char *p = in + (t14 * 1088u + t10 * 544u + t7 * 68u + t63 * 4u) * 4u;
-#endif
     uint4 D[2][2];
 #pragma unroll
     for (int b9 = 0; b9 < 2; b9++)
@@ -520,38 +318,19 @@ __global__ __launch_bounds__(1024) void k_acs_lds15(const uint16_t *__restrict__
       }
     }
     const unsigned qthr = (t14 << 11) | (t10 << 10) | (t7 << 7) | (t63 << 3);
-#if L15_ALIAS && !L15_DIRECTOUT
-    __syncthreads();            // every thread has pulled its level-3 slots: the region may now take the output image
-#endif
-    if constexpr (!(ABL & 1)) {
+    if constexpr (!NOARITH) {
       const unsigned d0_ = l15_stage<12>(r, qthr, x, sy, adj, rw3), d1_ = l15_stage<13>(r, qthr, x, sy, adj, rw3);
       const unsigned d2_ = l15_stage<14>(r, qthr, x, sy, adj, rw3);
-      if constexpr (ABL & 4) { if ((d0_ ^ d1_ ^ d2_) == 0x12345u) l15_dstore(L15_ROW(12), d0_); }
-      else { l15_dstore(L15_ROW(12), d0_); l15_dstore(L15_ROW(13), d1_); l15_dstore(L15_ROW(14), d2_); }
+      l15_dstore(L15_ROW(12), d0_); l15_dstore(L15_ROW(13), d1_); l15_dstore(L15_ROW(14), d2_);
     }
     v2u16 mnv_ = r[0];
 #pragma unroll
     for (int b = 1; b < 16; b++) mnv_ = __builtin_elementwise_min(mnv_, r[b]);
     mnv = mnv_;
     const unsigned rowb = (t7 << 7) | (t63 << 3);
-#if L15_DIRECTOUT
     // rows straight to HBM: row rowb + low3 of this tile's 64 KiB block, 8 bytes at column t14 << 3 | t10 << 2
     // (32 lanes x 8 B = the 256 bytes of the row; the other 32 lanes write row + 128)
-    {
-      unsigned char *o = reinterpret_cast<unsigned char *>(newm + (size_t)x * 32768u) + rowb * 256u + ((t14 << 3) | (t10 << 2)) * 2u;
-#pragma unroll
-      for (int l3 = 0; l3 < 8; l3++) {
-        uint2 w; w.x = as_u32(r[l3]); w.y = as_u32(r[8 + l3]);
-        if constexpr (ABL & 8) { if (w.x == 0x12345u && w.y == 77u) *reinterpret_cast<uint2 *>(o + l3 * 256) = w; }
-        else l15_mstore(o + l3 * 256, w);
-      }
-    }
-  }
-#undef L15_STAGES4
-#undef L15_ROW
-#else
-    // output image: row = t7 << 7 | t63 << 3 | low3, 8 bytes at column t14 << 3 | t10 << 2 | b9 << 1 | b8
-    unsigned char *o = outb + rowb * 256u + ((rowb >> 3) & 31u) * 16u + ((t14 << 3) | (t10 << 2)) * 2u;
+    unsigned char *o = reinterpret_cast<unsigned char *>(newm + (size_t)x * 32768u) + rowb * 256u + ((t14 << 3) | (t10 << 2)) * 2u;
 #pragma unroll
     for (int l3 = 0; l3 < 8; l3++) {
       uint2 w; w.x = as_u32(r[l3]); w.y = as_u32(r[8 + l3]);
@@ -560,44 +339,25 @@ __global__ __launch_bounds__(1024) void k_acs_lds15(const uint16_t *__restrict__
   }
 #undef L15_STAGES4
 #undef L15_ROW
-  __syncthreads();
-  // ---- store: 16-byte chunk g = row g >> 4, chunk g & 15; run of row L at phys (L << 15 | x << 7)
-  {
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const unsigned g = i * 1024 + th, row = g >> 4, c = g & 15u;
-      const uint4 o = *reinterpret_cast<const uint4 *>(outb + row * 256u + ((row >> 3) & 31u) * 16u + c * 16u);
-#if L15_WMAJOR
-      uint4 *dst = reinterpret_cast<uint4 *>(newm + (size_t)x * 32768u) + g;
-#else
-      uint4 *dst = reinterpret_cast<uint4 *>(newm + (((size_t)row << 15) | ((size_t)x << 7))) + c;
-#endif
-      if constexpr (ABL & 8) { if (o.x == 0x12345u && o.y == 77u) *dst = o; }
-      else *dst = o;
-    }
-  }
-#endif
 
   // ---- minimum of what this workgroup wrote, running offset, row layout codes
-  if constexpr (!(ABL & 16)) {
-    if constexpr (TOUT) {
-      unsigned mn = (unsigned)mnv.x < (unsigned)mnv.y ? (unsigned)mnv.x : (unsigned)mnv.y;
-      mn = wave_min_u32(mn);
-      if ((th & 63) == 0) s16[16 + (th >> 6)] = mn;
-      __syncthreads();
-      if (th == 0) {
-        unsigned m = s16[16];
+  if constexpr (TOUT) {
+    unsigned mn = (unsigned)mnv.x < (unsigned)mnv.y ? (unsigned)mnv.x : (unsigned)mnv.y;
+    mn = wave_min_u32(mn);
+    if ((th & 63) == 0) s16[16 + (th >> 6)] = mn;
+    __syncthreads();
+    if (th == 0) {
+      unsigned m = s16[16];
 #pragma unroll
-        for (int w = 1; w < 16; w++) m = s16[16 + w] < m ? s16[16 + w] : m;
-        ds->blkmin[(pass + 1) & 1][x] = m;
-        if (x == 0) ds->nmin[(pass + 1) & 1] = gridDim.x;
-      }
+      for (int w = 1; w < 16; w++) m = s16[16 + w] < m ? s16[16 + w] : m;
+      ds->blkmin[(pass + 1) & 1][x] = m;
+      if (x == 0) ds->nmin[(pass + 1) & 1] = gridDim.x;
     }
-    if (th == 0 && x == 0) {
-      ds->off += (long long)(int)adj;
-      for (int t = 0; t < 15; t++) { int rr = row0 + t; if (rr >= len) rr -= len; rowmeta[rr] = LDS15_META(t + 1); }
-    }
-  } else if (mnv.x == 0x7777 && th == 0) ds->off = 1;
+  }
+  if (th == 0 && x == 0) {
+    ds->off += (long long)(int)adj;
+    for (int t = 0; t < 15; t++) { int rr = row0 + t; if (rr >= len) rr -= len; rowmeta[rr] = LDS15_META(t + 1); }
+  }
 }
 
 // decision for NEW state s of the row written by stage tau (1..15) of an LDS15 pass; r = that row's base
@@ -610,25 +370,17 @@ __device__ __forceinline__ unsigned lds15_get_decision(const uint32_t *__restric
   else if (t < 8)  { th = ((q >> 11) << 6) | ((q >> 1) & 63u);    a = (q >> 7) & 15u; h = q & 1u; lb = 7u - t; }
   else if (t < 12) { th = ((q >> 7) << 2) | ((q >> 1) & 3u);      a = (q >> 3) & 15u; h = q & 1u; lb = 11u - t; }
   else {
-#if L15_DIRECTOUT
     th = (((q >> 3) & 15u) << 6) | ((q >> 11) << 2) | (((q >> 10) & 1u) << 1) | ((q >> 7) & 1u);
-#else
-    th = ((q >> 11) << 6) | (((q >> 7) & 1u) << 5) | (((q >> 10) & 1u) << 4) | ((q >> 3) & 15u);
-#endif
     a = (((q >> 9) & 1u) << 3) | (q & 7u); h = (q >> 8) & 1u; lb = 14u - t;
   }
   const unsigned bf = ((a >> (lb + 1u)) << lb) | (a & ((1u << lb) - 1u));
-#if L15_DECPERM
   const unsigned bit = 8u * (2u * ((a >> lb) & 1u) + h) + bf;
-#else
-  const unsigned bit = 16u * h + 2u * bf + ((a >> lb) & 1u);
-#endif
   return ((r[x * 1024u + th] >> bit) & 1u) ^ 1u;                  // rows hold NOT(decision)
 }
 
 // ---- layout conversion: natural <-> L15 ------------------------------------------------------------
 // Workgroup (h, mh): natural states s = h << 15 | (mh*64 + m) << 8 | l  (32 KiB contiguous), L15 position
-// l << 15 | h << 7 | mh*64 + m  (256 runs of 128 B).  Transposed through LDS, rows padded by one dword.
+// h << 15 | l << 7 | mh*64 + m  (256 runs of 128 B).  Transposed through LDS, rows padded by one dword.
 __global__ __launch_bounds__(512) void k_l15_from_nat(const uint16_t *__restrict__ nat, uint16_t *__restrict__ l15) {
   __shared__ uint16_t t[64 * 258];
   const unsigned th = threadIdx.x, h = blockIdx.x >> 1, mh = blockIdx.x & 1u;
@@ -643,11 +395,7 @@ __global__ __launch_bounds__(512) void k_l15_from_nat(const uint16_t *__restrict
   for (int i = 0; i < 16; i++) {                     // dword g: l = g >> 5, m pair = g & 31
     const unsigned g = i * 512 + th, l = g >> 5, mp = g & 31u;
     const unsigned v = (unsigned)t[(2 * mp) * 258 + l] | ((unsigned)t[(2 * mp + 1) * 258 + l] << 16);
-#if L15_WMAJOR
     reinterpret_cast<unsigned *>(l15 + ((size_t)h << 15) + (l << 7) + (mh << 6))[mp] = v;
-#else
-    reinterpret_cast<unsigned *>(l15 + ((size_t)l << 15) + (h << 7) + (mh << 6))[mp] = v;
-#endif
   }
 }
 __global__ __launch_bounds__(512) void k_l15_to_nat(const uint16_t *__restrict__ l15, uint16_t *__restrict__ nat) {
@@ -656,11 +404,7 @@ __global__ __launch_bounds__(512) void k_l15_to_nat(const uint16_t *__restrict__
 #pragma unroll 4
   for (int i = 0; i < 16; i++) {
     const unsigned g = i * 512 + th, l = g >> 5, mp = g & 31u;
-#if L15_WMAJOR
     const unsigned v = reinterpret_cast<const unsigned *>(l15 + ((size_t)h << 15) + (l << 7) + (mh << 6))[mp];
-#else
-    const unsigned v = reinterpret_cast<const unsigned *>(l15 + ((size_t)l << 15) + (h << 7) + (mh << 6))[mp];
-#endif
     t[(2 * mp) * 258 + l] = (uint16_t)v;
     t[(2 * mp + 1) * 258 + l] = (uint16_t)(v >> 16);
   }
@@ -673,9 +417,5 @@ __global__ __launch_bounds__(512) void k_l15_to_nat(const uint16_t *__restrict__
   }
 }
 __host__ __device__ constexpr unsigned l15_phys(unsigned s) {
-#if L15_WMAJOR
   return ((s >> 15) << 15) | ((s & 0xffu) << 7) | ((s >> 8) & 0x7fu);
-#else
-  return ((s & 0xffu) << 15) | (s >> 8);
-#endif
 }
